@@ -24,6 +24,17 @@ there is no data-path collective.
     own multi-device sharder (include/ecg_multi.h): one host thread +
     context per device.
 
+A plain run sets up, runs --warmup untimed steps, times --steps steps and
+prints one JSON line (`value`, `ms_per_step` = wall milliseconds per timed
+step, `roofline` from the HIP events recorded in those steps).  Everything
+else runs only with `--full`: the run's consistency check (`verified`), the
+configs[3] / configs[4] legs, the measured streaming ceilings, the detail
+rows and the CPU baseline described below (`--no-detail` / `--no-cpu` drop
+parts of it again).  `--dump-outputs DIR` writes what the last timed step
+computed -- the parity rows and the regenerated cells, a fixed seeded sample
+of them when they exceed the size cap (dump_outputs) -- as DIR/<name>.npy;
+the inputs are seeded, so two builds can be compared output for output.
+
 roofline: the dominant kernel (ecg_mm_kernel<4,2>, which serves both the
 encode and the 2-erasure decode) -- algorithmic bytes per launch
 (k+rows)*C*S / mean launch duration from HIP events on its stream, against
@@ -81,8 +92,15 @@ def parse(argv=None):
                     help="procs: one process per GPU; lib: one process, the library's ecg_multi sharder")
     ap.add_argument("--allow-shared-device", action="store_true",
                     help="permit more ranks/shards than visible devices (rehearsal on a small box)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run its consistency check (`verified`), the configs[3] / "
+                         "configs[4] legs, the measured streaming ceilings, the detail rows and the CPU "
+                         "baseline (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last step computed (parity rows, regenerated "
+                         "cells) as DIR/<name>.npy in float32; a fixed seeded sample of outputs over the size cap")
     ap.add_argument("--cpu-seconds", type=float, default=16.0, help="CPU baseline time budget (headline runs; the per-config rows take about as long again)")
-    ap.add_argument("--no-detail", action="store_true", help="skip the extra per-config rows")
+    ap.add_argument("--no-detail", action="store_true", help="with --full: skip the extra per-config rows")
     ap.add_argument("--host-chunk", type=int, default=0,
                     help=f"stripes per staging chunk of the host-resident workloads (default {HOST_CHUNK})")
     ap.add_argument("--no-cpu", action="store_true")
@@ -334,6 +352,37 @@ class Workload:
             out["encode_parity_decodes_to_data"] = ok
         return out
 
+    def outputs(self):
+        """What a step's caller receives, as (name, logical bytes, read(off, n))
+        over the dense logical array: the encode's parity [p][S][C] (the row
+        padding skipped) and the decode's regenerated cells [S][nerrs][C]."""
+        import numpy as np
+
+        k, p, C, S = self.k, self.p, self.C, self.S
+        if S == 0:
+            return []
+
+        def runs(buf, off, n, inner, dev_off):
+            # bytes [off, off + n) of a dense [..][inner] array whose rows sit at dev_off(row)
+            parts = []
+            while n > 0:
+                row, within = divmod(off, inner)
+                m = min(n, inner - within)
+                parts.append(buf.download(m, offset=dev_off(row) + within))
+                off, n = off + m, n - m
+            return parts[0] if len(parts) == 1 else np.concatenate(parts)
+
+        out = []
+        if "enc" in self.ops:
+            out.append(("parity", p * S * C,
+                        lambda off, n: runs(self.parity, off, n, S * C, lambda r: r * self.prow)))
+        if "dec" in self.ops:
+            ne, st = len(self.err), (k + p) * C
+            out.append(("recovered", S * ne * C,
+                        lambda off, n: runs(self.stripes, off, n, C,
+                                            lambda c: (c // ne) * st + self.err[c % ne] * C)))
+        return out
+
     def user_bytes_per_step(self):
         return len(self.ops) * self.k * self.C * self.S
 
@@ -401,6 +450,27 @@ class HostWorkload:
         if "dec_host" in self.ops:
             n += len(self.err) * self.C * self.S
         return n
+
+    def outputs(self):
+        """As Workload.outputs, read from the pinned host buffers: parity
+        [p][S][C] and the regenerated cells [S][nerrs][C].  Read before
+        verify(), which decodes once more into the image."""
+        import numpy as np
+
+        k, p, C, S = self.k, self.p, self.C, self.S
+        out = []
+        if "enc_host" in self.ops:
+            out.append(("parity", p * S * C, lambda off, n: self.parity.array[off:off + n].copy()))
+        if "dec_host" in self.ops:
+            ne = len(self.err)
+            img = self.stripes.array.reshape(S, k + p, C)
+
+            def read(off, n):
+                cells = range(off // C, (off + n - 1) // C + 1)
+                flat = np.concatenate([img[c // ne, self.err[c % ne]] for c in cells])
+                return flat[off - cells[0] * C:off - cells[0] * C + n].copy()
+            out.append(("recovered", S * ne * C, read))
+        return out
 
     def verify(self):
         """Recovered cells (MARKER before the first step) equal the original
@@ -489,6 +559,9 @@ class MultiWorkload:
     def kernel_ms(self):
         return self.shards[0].kernel_ms()
 
+    def outputs(self):
+        return [(f"{name}_shard{i}", n, read) for i, w in enumerate(self.shards) for name, n, read in w.outputs()]
+
     def verify(self):
         out = {}
         for w in self.shards:
@@ -505,6 +578,45 @@ class MultiWorkload:
     def free(self):
         for w in self.shards:
             w.free()
+
+
+# ------------------------------------------------------------------ outputs
+DUMP_PIECE = 4096               # bytes per sampled piece
+DUMP_BYTES = 12 << 20           # output bytes written per run, all arrays and ranks together (x4 as float32)
+DUMP_SEED = 0xDA05D0
+
+
+def dump_pieces(nbytes, share, i):
+    """Ascending piece indices (units of DUMP_PIECE bytes) sampled from the
+    i-th output array of nbytes > share bytes: the first, the last, and
+    seeded draws without replacement, share bytes in all."""
+    import numpy as np
+
+    npieces = -(-nbytes // DUMP_PIECE)
+    rng = np.random.default_rng(DUMP_SEED + i)
+    take = rng.choice(npieces - 2, size=share // DUMP_PIECE - 2, replace=False) + 1
+    return np.sort(np.concatenate([[0, npieces - 1], take]))
+
+
+def dump_outputs(wl, path, world=1, rank=0):
+    """--dump-outputs: the arrays of wl.outputs() as <path>/<name>.npy
+    (<name>_rank<r>.npy when there are several ranks), bytes as float32.  An
+    array within its share of DUMP_BYTES is written whole; of a larger one,
+    pieces of DUMP_PIECE bytes at offsets drawn once from a fixed seed (the
+    first and the last piece always among them), in ascending order -- the
+    same bytes of the same inputs in every run and every build."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    outs = wl.outputs()
+    share = DUMP_BYTES // max(1, world * len(outs))
+    for i, (name, nbytes, read) in enumerate(outs):
+        if nbytes <= share:
+            a = read(0, nbytes)
+        else:
+            a = np.concatenate([read(int(j) * DUMP_PIECE, min(DUMP_PIECE, nbytes - int(j) * DUMP_PIECE))
+                                for j in dump_pieces(nbytes, share, i)])
+        np.save(os.path.join(path, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a.astype(np.float32))
 
 
 # ------------------------------------------------------------------ measurements
@@ -1299,8 +1411,8 @@ def host_report(args, ctx, wl, world, rank, value, elapsed, ranks, nshard=1):
     is null and `pcie` sets the achieved H2D rate against this box's raw
     pinned copy rate (measured on rank 0 at N=1)."""
     k, p, C, S = wl.k, wl.p, wl.C, wl.S
-    ver = wl.verify()
-    allver = gather(world, ver)
+    ver = wl.verify() if args.full else None
+    allver = gather(world, ver or {})
     ok = all(all(v.values()) for v in allver)
     h2d = wl.h2d_bytes_per_step() * args.steps * world / elapsed / 1e9
     d2h = wl.d2h_bytes_per_step() * args.steps * world / elapsed / 1e9
@@ -1332,7 +1444,7 @@ def host_report(args, ctx, wl, world, rank, value, elapsed, ranks, nshard=1):
         "cpu_baseline": None,
     }
     wl.free()
-    if rank == 0 and world == 1 and nshard == 1 and not args.no_detail:
+    if rank == 0 and world == 1 and nshard == 1 and args.full and not args.no_detail:
         raw = pinned_copy_rates(ctx)
         out["pcie"]["measured_pinned_GBps"] = raw
         out["pcie"]["frac_of_h2d"] = round(h2d / raw["h2d"], 4)
@@ -1352,7 +1464,7 @@ def rehearse(args, world, rank, local):
         time.sleep(0.001 * (1 + rank))
     elapsed = max_over_ranks(world, time.perf_counter() - t0)
     ranks = gather(world, {"rank": rank, "local_rank": local, "pid": os.getpid()})
-    legs = config_legs(args, None, world, rank, None) if args.workload == "enc_dec_4p2" else {}
+    legs = config_legs(args, None, world, rank, None) if args.full and args.workload == "enc_dec_4p2" else {}
     if rank == 0:
         print(json.dumps({"metric": "rehearsal (no GPU work)", "rehearsal": True, "value": None, "n_ranks": world,
                           "steps": args.steps, "ms_per_step": round(elapsed / max(1, args.steps) * 1e3, 3),
@@ -1364,6 +1476,8 @@ def main():
     args = parse()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and args.sharder == "procs":
         sys.exit(launch_ranks(args))          # parent: no GPU calls before or after
     numa_info = rank_numa(args)               # before anything starts the GPU runtime
@@ -1438,6 +1552,9 @@ def main():
     barrier(world)
     elapsed = max_over_ranks(world, mine)  # the job took as long as its slowest rank
 
+    if args.dump_outputs:                  # what the last timed step left, before anything else runs
+        dump_outputs(wl, args.dump_outputs, world, rank)
+
     if args.profile_only:
         wl.free()
         if m is not None:
@@ -1486,8 +1603,8 @@ def main():
         traffic = pmc.get("hbm_bytes_per_launch")
         traffic_src = (f"{pmc['_path']} (rocprofv3 --pmc FETCH_SIZE and WRITE_SIZE passes of this "
                        "workload, FETCH x2 per the gfx950 correction; copied, not measured in this run)")
-    ver = wl.verify()
-    allver = gather(world, ver)
+    ver = wl.verify() if args.full else None
+    allver = gather(world, ver or {})
     ok = all(all(v.values()) for v in allver)
 
     par = (f"stripe-sharded x{nshard} in one process (ecg_multi), no collective" if m is not None
@@ -1523,11 +1640,11 @@ def main():
     }
     wl.free()
     legs = {}
-    if args.workload == "enc_dec_4p2" and m is None and not args.no_detail:
+    if args.full and args.workload == "enc_dec_4p2" and m is None and not args.no_detail:
         legs = config_legs(args, ctx, world, rank, numa_info)
         out["detail"] = dict(legs)
         ok = ok and all(v["verified"] for v in legs.values())
-    if rank == 0 and world == 1 and not args.no_detail:
+    if args.full and rank == 0 and world == 1 and not args.no_detail:
         ceil = measured_ceilings(ctx)
         mix = mix_ceiling(ceil, k / (k + p))      # enc (k in, p out) and dec (k in, 2 out) alike at p = 2
         out["roofline"]["measured_stream_GBps"] = ceil
@@ -1544,7 +1661,7 @@ def main():
                        "read_frac = the k input cells alone / t / 8 TB/s.  The same launch must also write "
                        "p/k as many bytes, and this box's HBM streams 6.7-7.0 TB/s read-only, so read_frac "
                        "cannot reach 0.70 while parity is written (DESIGN.md §6)"}
-    if rank == 0 and world == 1 and not args.no_cpu and m is None:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and m is None:
         out["cpu_baseline"] = cpu_baseline(k, p, C, args.cpu_seconds, ops)
         if "detail" in out:                   # CPU beside GPU, per config
             for name, row in out["cpu_baseline"].get("configs", {}).items():

@@ -92,11 +92,12 @@ def test_bench_gpus_n_spawns_ranks():
     """`bench.py --gpus 2` with no launcher in the environment starts two
     rank processes itself (gloo rendezvous on 127.0.0.1) and rank 0 prints
     ONE aggregated line: max-over-ranks time (rank 1 sleeps twice as long)
-    and both ranks listed.  --rehearse replaces the GPU work with sleeps."""
+    and both ranks listed.  --rehearse replaces the GPU work with sleeps;
+    --full adds the configs[3] / configs[4] legs to the headline."""
     import json
 
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20",
-                        "--rehearse"], env=_bench_env(), capture_output=True, text=True, timeout=300)
+                        "--rehearse", "--full"], env=_bench_env(), capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -125,6 +126,69 @@ def test_bench_gpus_n_spawns_ranks():
         assert abs(r["frac_of_fair_share_h2d"] / (r["h2d_GBps"] / r["fair_share_h2d_GBps"]) - 1) < 1e-2   # rounding
         if r.get("measured_pinned_GBps"):
             assert abs(r["frac_of_h2d"] / (r["h2d_GBps"] / r["measured_pinned_GBps"]["h2d"]) - 1) < 1e-2
+
+
+def test_bench_plain_run_has_no_legs():
+    """Without --full a run times its steps and nothing else: the rehearsal
+    line carries ms_per_step and an empty detail."""
+    import json
+
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "1",
+                        "--rehearse"], env=_bench_env(), capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stdout + r.stderr
+    d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][0])
+    assert d["steps"] == 7 and d["ms_per_step"] >= 1.0 and d["detail"] == {}
+
+
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: a small output is written whole, a large one as the
+    same seeded pieces in every run (first and last piece included), as
+    float32 within the size cap; pieces are read across padded rows."""
+    sys.path.insert(0, ROOT)
+    import numpy as np
+
+    import bench
+
+    big = np.random.default_rng(1).integers(0, 256, 64 << 20, dtype=np.uint8)
+    small = np.arange(5000, dtype=np.uint8)
+
+    class Wl:
+        def outputs(self):
+            return [("parity", big.size, lambda off, n: big[off:off + n]),
+                    ("recovered", small.size, lambda off, n: small[off:off + n])]
+
+    for d in ("a", "b"):
+        bench.dump_outputs(Wl(), str(tmp_path / d))
+    a, b = (np.load(tmp_path / d / "parity.npy") for d in ("a", "b"))
+    assert a.dtype == np.float32 and np.array_equal(a, b)
+    assert a.size == bench.DUMP_BYTES // 2 and a.size % bench.DUMP_PIECE == 0
+    assert np.array_equal(a[:bench.DUMP_PIECE], big[:bench.DUMP_PIECE])
+    assert np.array_equal(a[-bench.DUMP_PIECE:], big[-bench.DUMP_PIECE:])
+    assert np.array_equal(np.load(tmp_path / "a" / "recovered.npy"), small.astype(np.float32))
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64 << 20
+
+    # Workload.outputs() maps the dense [p][S][C] parity onto rows with padding between them
+    k, p, C, S = 2, 2, 96, 3
+    wl = bench.Workload.__new__(bench.Workload)
+    wl.k, wl.p, wl.C, wl.S, wl.err, wl.ops, wl.prow = k, p, C, S, [0, 1], ("enc", "dec"), S * C + 32
+
+    class Buf:
+        def __init__(self, a):
+            self.a = a
+
+        def download(self, n, offset=0):
+            return self.a[offset:offset + n].copy()
+
+    rng = np.random.default_rng(2)
+    wl.parity = Buf(rng.integers(0, 256, p * wl.prow, dtype=np.uint8))
+    wl.stripes = Buf(rng.integers(0, 256, S * (k + p) * C, dtype=np.uint8))
+    (pn, pbytes, pread), (rn, rbytes, rread) = wl.outputs()
+    assert (pn, pbytes, rn, rbytes) == ("parity", p * S * C, "recovered", S * 2 * C)
+    want = np.concatenate([wl.parity.a[r * wl.prow:r * wl.prow + S * C] for r in range(p)])
+    assert np.array_equal(pread(0, pbytes), want) and np.array_equal(pread(S * C - 5, 9), want[S * C - 5:S * C + 4])
+    img = wl.stripes.a.reshape(S, k + p, C)
+    assert np.array_equal(rread(0, rbytes), img[:, [0, 1]].reshape(-1))
+
 
 def test_strong_split_ranges():
     """configs[3]'s 8192 stripes cut into contiguous ranges that cover the

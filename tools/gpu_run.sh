@@ -33,7 +33,7 @@ for what in "$@"; do
 		rc=$?; [ $rc -le 1 ] || exit $rc
 		;;
 	bench)
-		step bench 900 python bench.py || exit $?
+		step bench 900 python bench.py --full || exit $?
 		;;
 	prof)             # kernel trace + stats of the headline (profiles/rNN/rocprof_stats)
 		rm -rf "$O/prof"
@@ -90,15 +90,15 @@ for what in "$@"; do
 		done
 		;;
 	rehearse8)        # 8 ranks on this one GPU: rendezvous, NUMA pinning, legs, accounting (no scaling)
-		step bench_rehearse8 900 python bench.py --gpus 8 --allow-shared-device --steps 10 --warmup 2 --no-cpu \
+		step bench_rehearse8 900 python bench.py --gpus 8 --allow-shared-device --steps 10 --warmup 2 --full --no-cpu \
 			|| exit $?
 		;;
 	dist2)            # 2 ranks through torch.distributed.run, one GPU shared
 		step dist2 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 \
-			--master-port 29533 bench.py --gpus 2 --allow-shared-device --steps 5 --warmup 2 --no-cpu || exit $?
+			--master-port 29533 bench.py --gpus 2 --allow-shared-device --steps 5 --warmup 2 --full --no-cpu || exit $?
 		;;
 	hoststream)
-		step hoststream_n1 300 python bench.py --workload rebuild_stream_8p2 --steps 5 --warmup 1 || exit $?
+		step hoststream_n1 300 python bench.py --workload rebuild_stream_8p2 --steps 5 --warmup 1 --full || exit $?
 		;;
 	ecab)             # EC_LIBS="name=path ...": product-kernel builds A/B (tools/ec_ab.py)
 		step ec_ab 1000 python tools/ec_ab.py base=daos_amd/lib/libecg.so ${EC_LIBS:-} || exit $?
