@@ -233,6 +233,11 @@ typedef struct ecg_mmcs_params {
 	uint32_t nitems;
 	uint32_t pad3;
 	uint32_t row_slot[ECG_KMAX_R];
+	/* source checksums (the SRC instantiations; NULL = outputs only):
+	 * src_out[(src_slot[j] * nstripes + s) * nch + c] = checksum of chunk c of
+	 * source cell j of stripe s, zeroed by the host like out */
+	uint8_t *src_out;
+	uint32_t src_slot[ECG_KMAX_K];
 } ecg_mmcs_params_t;
 
 /*
@@ -284,9 +289,15 @@ int ecg_k_launch_matmul_sel(const ecg_mm_params_t *p, const uint8_t *sel_dev, ui
 int ecg_k_launch_copy(const void *src, void *dst, uint64_t bytes, int mode, void *stream,
 		      uint32_t max_blocks, uint32_t *kernel_id);
 /* Fused product + checksum (kernels/ecg_fused_kernels.hip).  Returns 1 (and
- * launches nothing) when the operands are not 16-byte aligned. */
+ * launches nothing) when the operands are not 16-byte aligned, or when
+ * q->src_out is set and the shape has no SRC instantiation. */
 int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs_params_t *q,
 			     const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
+/* Compare n checksums of len (2, 4 or 8) bytes: result[0] += mismatches,
+ * result[1] = min(result[1], lowest mismatching index); the host presets
+ * result to {0, UINT64_MAX} (kernels/ecg_csum_kernels.hip). */
+int ecg_k_launch_csum_compare(const void *got, const void *want, uint64_t n, uint32_t len,
+			      uint64_t *result, void *stream, uint32_t *kernel_id);
 #define ECG_KID_FUSED 500u	/* fused kernel ids start here (below ECG_KID_COPY_SEGS) */
 const char *ecg_k_fused_kernel_name(uint32_t kernel_id);
 /* The common alignment (16, 8, 4 or 1 bytes) of every cell address of a

@@ -553,10 +553,15 @@ static int aligned16_ok(const void *src, const int64_t *soff, int k, int64_t sst
 	return (bits & 15u) == 0;
 }
 
-int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, uint64_t C,
-		    uint32_t S, const void *src, const int64_t *soff, int64_t sstride, void *dst,
-		    const int64_t *doff, int64_t dstride, int type, uint64_t chunksize,
-		    uint64_t rec_size, void *csums, const uint32_t *row_slot, void *stream)
+/* src_csums (may be NULL) / src_slot: checksums of the source cells too,
+ * src_csums[src_slot[j]][s][chunk] -- from the fused kernel's SRC instantiation
+ * where the route (ecg_csum_all_route) picks it, else the outputs as without
+ * them and one ecg_csum_extents launch per source cell. */
+static int matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, uint64_t C,
+		       uint32_t S, const void *src, const int64_t *soff, int64_t sstride, void *dst,
+		       const int64_t *doff, int64_t dstride, int type, uint64_t chunksize,
+		       uint64_t rec_size, void *csums, const uint32_t *row_slot, void *src_csums,
+		       const uint32_t *src_slot, void *stream)
 {
 	const int cl = ecg_csum_len(type);
 	ecg_mmcs_params_t q;
@@ -575,11 +580,17 @@ int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 		return rc;
 	ecg_gf_init();
 	st = ecg_pick_stream(ctx, stream);
+	if (src_csums && (!ecg_csum_all_route(ctx, type, k, rows) ||
+			  (uintptr_t)src_csums % (type == ECG_HASH_CRC64 ? 8u : 4u) ||
+			  !aligned16_ok(src, soff, k, sstride, dst, doff, rows, dstride)))
+		goto two_pass_src;
 	if (k <= ECG_KMAX_K && rows <= ECG_KMAX_R) {
-		fused = ecg_csum_fused_params(ctx, type, chunksize, rec_size, C, k, rows, csums, &q);
+		fused = ecg_csum_fused_params(ctx, type, chunksize, rec_size, C, k, rows, csums, src_csums != NULL, &q);
 		if (fused < 0)
 			return fused;
 	}
+	if (src_csums && !fused)
+		goto two_pass_src;
 	if (fused) {
 		ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
 		uint32_t kid = 0;
@@ -595,8 +606,12 @@ int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 		prm->nstripes = S;
 		prm->k = (uint32_t)k;
 		prm->rows = (uint32_t)rows;
-		for (j = 0; j < k; j++)
+		for (j = 0; j < k; j++) {
 			prm->src_cell_off[j] = soff[j];
+			if (src_csums)
+				q.src_slot[j] = src_slot[j];
+		}
+		q.src_out = src_csums;
 		for (r = 0; r < rows; r++) {
 			prm->dst_cell_off[r] = doff[r];
 			q.row_slot[r] = row_slot[r];
@@ -607,6 +622,8 @@ int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 		if (aligned16_ok(src, soff, k, sstride, dst, doff, rows, dstride)) {
 			hipError_t he = hipMemsetAsync(csums, 0, (size_t)rows * S * q.nch * (size_t)cl, st);
 
+			if (he == hipSuccess && src_csums)
+				he = hipMemsetAsync(src_csums, 0, (size_t)k * S * q.nch * (size_t)cl, st);
 			if (he != hipSuccess) {
 				free(prm);
 				return ecg_hip_fail(he, "csum memset");
@@ -616,13 +633,16 @@ int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 		free(prm);
 		if (e == 0) {
 			ECG_STAT_ADD(ctx, launches, 1);
-			ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)rows * S * q.nch);
+			ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)(rows + (src_csums ? k : 0)) * S * q.nch);
 			ecg_set_last_kernel(ecg_k_kernel_name(kid));
 			return 0;
 		}
 		if (e != 1)
 			return ecg_hip_fail((hipError_t)e, "fused kernel launch");
-		/* e == 1: operands not 16-byte aligned -> two-pass path */
+		/* e == 1: operands not 16-byte aligned (or no SRC instantiation of
+		 * the shape) -> two-pass path */
+		if (src_csums)
+			goto two_pass_src;
 	}
 	rc = matmul2(ctx, k, rows, coef, C, S, src, soff, sstride, NULL, NULL, 0, dst, doff, dstride,
 		     0, (void *)st);
@@ -638,6 +658,114 @@ int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 			return rc;
 	}
 	return 0;
+
+two_pass_src:
+	/* the outputs as ecg_matmul_csum computes them (its fused kernel where
+	 * the shape allows), then each source cell's S extents, on the stream */
+	rc = matmul_csum(ctx, k, rows, coef, C, S, src, soff, sstride, dst, doff, dstride, type, chunksize,
+			 rec_size, csums, row_slot, NULL, NULL, (void *)st);
+	if (rc)
+		return rc;
+	nch = ecg_csum_chunk_count(chunksize, rec_size, 0, C / rec_size);
+	for (r = 0; r < k; r++) {
+		rc = ecg_csum_extents(ctx, type, chunksize, rec_size, 0, C / rec_size,
+				      (const uint8_t *)src + soff[r], sstride, S,
+				      (uint8_t *)src_csums + (uint64_t)src_slot[r] * S * nch * (uint64_t)cl,
+				      (void *)st);
+		if (rc)
+			return rc;
+	}
+	return 0;
+}
+
+int ecg_matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, uint64_t C,
+		    uint32_t S, const void *src, const int64_t *soff, int64_t sstride, void *dst,
+		    const int64_t *doff, int64_t dstride, int type, uint64_t chunksize,
+		    uint64_t rec_size, void *csums, const uint32_t *row_slot, void *stream)
+{
+	return matmul_csum(ctx, k, rows, coef, C, S, src, soff, sstride, dst, doff, dstride, type, chunksize,
+			   rec_size, csums, row_slot, NULL, NULL, stream);
+}
+
+int ecg_encode_csum_all(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, const void *data,
+			int64_t data_stripe_stride, void *parity, int64_t parity_cell_stride,
+			int64_t parity_stripe_stride, int type, uint64_t chunksize, uint64_t rec_size,
+			void *data_csums, void *parity_csums, void *stream)
+{
+	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
+	int64_t soff[ECG_MAX_K], doff[ECG_MAX_P];
+	uint32_t slot[ECG_MAX_P], sslot[ECG_MAX_K];
+	int i, rc;
+
+	rc = check_kp(k, p);
+	if (rc)
+		return rc;
+	if (ecg_csum_len(type) < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "csum: hash type %d not supported", type);
+	if (data == NULL || parity == NULL || data_csums == NULL || parity_csums == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "encode_csum_all: NULL buffer");
+	ecg_gen_cauchy1(k, p, en);
+	for (i = 0; i < k; i++) {
+		soff[i] = (int64_t)i * (int64_t)C;
+		sslot[i] = (uint32_t)i;
+	}
+	for (i = 0; i < p; i++) {
+		doff[i] = (int64_t)i * parity_cell_stride;
+		slot[i] = (uint32_t)i;
+	}
+	rc = matmul_csum(ctx, k, p, &en[k * k], C, S, data, soff, data_stripe_stride, parity, doff,
+			 parity_stripe_stride, type, chunksize, rec_size, parity_csums, slot, data_csums, sslot,
+			 stream);
+	if (rc == 0) {
+		ECG_STAT_ADD(ctx, encode_stripes, S);
+		ECG_STAT_ADD(ctx, encode_bytes, (uint64_t)k * C * S);
+	}
+	return rc;
+}
+
+int ecg_recover_csum_all(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *stripes,
+			 int64_t stripe_stride, const uint32_t *err_list, int nerrs, int type,
+			 uint64_t chunksize, uint64_t rec_size, void *csums, void *src_csums,
+			 uint32_t *src_idx, void *stream)
+{
+	struct ecg_rcache_ent ent;
+	int64_t soff[ECG_MAX_K], doff[ECG_MAX_P];
+	uint32_t slot[ECG_MAX_P], sslot[ECG_MAX_K];
+	int i, j, rc;
+
+	rc = check_kp(k, p);
+	if (rc)
+		return rc;
+	if (ecg_csum_len(type) < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "csum: hash type %d not supported", type);
+	if (err_list == NULL || stripes == NULL || csums == NULL || src_csums == NULL || src_idx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "recover_csum_all: NULL argument");
+	if (nerrs > p)
+		return ecg_fail(-ECG_DER_DATA_LOSS, "recover_csum_all: %d erasures > p=%d", nerrs, p);
+	if (nerrs <= 0)
+		return 0;
+	rc = recov_lookup(ctx, k, p, err_list, nerrs, &ent);
+	if (rc)
+		return rc;
+	for (i = 0; i < ent.k; i++) {
+		soff[i] = (int64_t)ent.dec_idx[i] * (int64_t)C;
+		sslot[i] = (uint32_t)i;
+		src_idx[i] = ent.dec_idx[i];
+	}
+	for (i = 0; i < ent.nerrs; i++) {
+		doff[i] = (int64_t)ent.out_idx[i] * (int64_t)C;
+		slot[i] = 0;
+		for (j = 0; j < nerrs; j++)	/* checksum rows in err_list order */
+			if (err_list[j] == ent.out_idx[i])
+				slot[i] = (uint32_t)j;
+	}
+	rc = matmul_csum(ctx, ent.k, ent.nerrs, ent.rows, C, S, stripes, soff, stripe_stride, stripes, doff,
+			 stripe_stride, type, chunksize, rec_size, csums, slot, src_csums, sslot, stream);
+	if (rc == 0) {
+		ECG_STAT_ADD(ctx, recover_stripes, S);
+		ECG_STAT_ADD(ctx, recover_bytes, (uint64_t)ent.nerrs * C * S);
+	}
+	return rc;
 }
 
 int ecg_encode_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, const void *data,

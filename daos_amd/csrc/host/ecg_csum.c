@@ -461,7 +461,7 @@ static void fused_cols_init(void)
 		g_fused_cols_env = 0;
 }
 
-static uint32_t fused_cols(const ecg_ctx_t *ctx, uint64_t m, int type, int k, int rows)
+static uint32_t fused_cols(const ecg_ctx_t *ctx, uint64_t m, int type, int k, int rows, int src)
 {
 	/* tools/fused_libs.py, profiles/r02/fused_libs/, profiles/r03/fused_tail/:
 	 * one output row (a parity shard's rebuild) 4; >= 2 rows: 4 for k >= 8
@@ -470,7 +470,13 @@ static uint32_t fused_cols(const ecg_ctx_t *ctx, uint64_t m, int type, int k, in
 	/* round 3, after the item tail stopped reading HBM: crc32 at EC_8P2 (byte
 	 * tables) walks 2 columns best -- +6.0 / +7.3 % vs +9.0 / +9.9 % at 4 on two
 	 * boxes; k = 16 and one or three rows keep 4 (profiles/r03/fused_cols/) */
-	const uint64_t dflt = type == ECG_HASH_CRC32 && k == 8 && rows == 2 ? 2 : rows == 1 ? 4 : k >= 8 ? 4 : 8;
+	/* the SRC instantiations finish k + rows registers per item: 8 columns for
+	 * every measured shape (tools/bench_csum_all.py --sweep-cols,
+	 * profiles/r07/csum_all/: EC_8P2 x 512 x 1 MiB crc32 1.58 ms at 2 columns,
+	 * 1.43 at 4, 1.33 at 8, 1.33 at 16; crc64 2.39 / 2.00 / 1.83 / 1.82;
+	 * EC_16P2 x 1024 x 128 KiB crc32 0.73 / 0.65 / 0.63 / 0.62) */
+	const uint64_t dflt = src ? 8
+			    : type == ECG_HASH_CRC32 && k == 8 && rows == 2 ? 2 : rows == 1 ? 4 : k >= 8 ? 4 : 8;
 	const int env = ctx->fused_cols ? (int)ctx->fused_cols
 					: (pthread_once(&g_fused_cols_once, fused_cols_init), g_fused_cols_env);
 
@@ -674,6 +680,22 @@ int ecg_set_csum_launch(ecg_ctx_t *ctx, uint32_t max_blocks)
 	return 0;
 }
 
+/* The measured default of ecg_csum_all_route: 1 = fused.  tools/
+ * bench_csum_all.py (profiles/r07/csum_all/, 32 KiB chunks, 3 alternating
+ * rounds, ms fused / two passes): crc32 EC_8P2 x 512 x 1 MiB 1.33 / 1.62,
+ * EC_4P2 x 1024 x 1 MiB 1.51 / 1.82, EC_16P2 x 1024 x 128 KiB 0.63 / 0.80;
+ * crc64 EC_16P2 0.83 / 0.85 -- fused.  crc64 EC_8P2 1.87 / 1.80 and EC_4P2
+ * 1.97 / 1.99 (won one run of the tool, lost another): two passes, as for
+ * every shape not measured (crc16, one or three output rows, other k). */
+static int csum_all_fused_default(int type, int k, int rows)
+{
+	if (rows != 2)
+		return 0;
+	if (type == ECG_HASH_CRC32)
+		return k == 4 || k == 8 || k == 16;
+	return type == ECG_HASH_CRC64 && k == 16;
+}
+
 int ecg_set_fused_cols(ecg_ctx_t *ctx, uint32_t ncols)
 {
 	if (ctx == NULL || ncols > 4096)
@@ -682,12 +704,65 @@ int ecg_set_fused_cols(ecg_ctx_t *ctx, uint32_t ncols)
 	return 0;
 }
 
+int ecg_set_csum_all_route(ecg_ctx_t *ctx, uint32_t route)
+{
+	if (ctx == NULL || route > 2)
+		return ecg_fail(-ECG_DER_INVAL, "set_csum_all_route: bad arguments");
+	ctx->csum_all_route = route;
+	return 0;
+}
+
+/* Whether ecg_encode_csum_all / ecg_recover_csum_all try the fused kernel's
+ * SRC instantiation for a shape (1) or run two passes (0).  The default is
+ * the fused route only where tools/bench_csum_all.py measured it faster than
+ * the two passes by more than their round-to-round spread (DESIGN §11,
+ * profiles/r07/csum_all/); shapes it did not measure run two passes. */
+int ecg_csum_all_route(const ecg_ctx_t *ctx, int type, int k, int rows)
+{
+	if (ctx->csum_all_route)
+		return ctx->csum_all_route == 1;
+	return csum_all_fused_default(type, k, rows);
+}
+
+int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want, uint64_t n,
+		     void *result, void *stream)
+{
+	const int cl = ecg_csum_len(type);
+	hipStream_t st;
+	hipError_t he;
+	uint32_t kid = 0;
+	int rc, e;
+
+	if (cl < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "csum_compare: hash type %d not supported", type);
+	if (ctx == NULL || result == NULL || (uintptr_t)result % 8u || (n && (got == NULL || want == NULL)))
+		return ecg_fail(-ECG_DER_INVAL, "csum_compare: bad arguments");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	he = hipMemsetAsync(result, 0, 8, st);
+	if (he == hipSuccess)
+		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
+	if (he != hipSuccess)
+		return ecg_hip_fail(he, "csum_compare memset");
+	if (n == 0)
+		return 0;
+	e = ecg_k_launch_csum_compare(got, want, n, (uint32_t)cl, result, (void *)st, &kid);
+	if (e != 0)
+		return ecg_hip_fail((hipError_t)e, "csum_compare kernel launch");
+	ECG_STAT_ADD(ctx, launches, 1);
+	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	return 0;
+}
+
 /* Fused product + checksum parameters (ecg_kabi.h) for output cells of C
  * bytes that start on chunk boundaries.  Returns 1 when the fused kernels
  * can take the request, 0 when the caller must run the product and
- * ecg_csum_extents separately, < 0 on error. */
+ * ecg_csum_extents separately, < 0 on error.  src: for the SRC instantiations
+ * (their own default columns per item). */
 int ecg_csum_fused_params(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
-			  uint64_t C, int k, int rows, void *csums, ecg_mmcs_params_t *q)
+			  uint64_t C, int k, int rows, void *csums, int src, ecg_mmcs_params_t *q)
 {
 	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
 	const struct crc_def *d;
@@ -717,7 +792,7 @@ int ecg_csum_fused_params(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t
 	m = rcs / ECG_MMCS_STRIDE;
 	q->m = (uint32_t)m;
 	q->m_last = (uint32_t)((last + ECG_MMCS_STRIDE - 1) / ECG_MMCS_STRIDE);
-	q->ncols = fused_cols(ctx, m, type, k, rows);
+	q->ncols = fused_cols(ctx, m, type, k, rows, src);
 	/* bound the multiplier table (nh + nh_last rows of 256 entries) for
 	 * very long chunks: at most 2048 items per chunk */
 	if ((m + q->ncols - 1) / q->ncols > 2048)

@@ -611,10 +611,62 @@ __host__ inline bool kind_ok(const csum_entry &e, const ecg_csum_params_t *p)
 	return e.type == 7 || e.tk == (e.aligned ? TK_4 : TK_5);
 }
 
+// Compare n checksums of LEN bytes (ecg_csum_compare): grid-stride, each
+// thread counts its mismatches and keeps the lowest index; threads that saw
+// one add to result[0] and lower result[1] ({0, UINT64_MAX} on entry).  Byte
+// loads: the arrays need no alignment, and n is small next to the cells.
+template <int LEN>
+__global__ void __launch_bounds__(CS_BLOCK)
+ecg_csum_compare_kernel(const uint8_t *got, const uint8_t *want, uint64_t n, unsigned long long *result)
+{
+	unsigned long long cnt = 0, lo = ~0ull;
+
+	for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+		uint32_t d = 0;
+
+#pragma unroll
+		for (int b = 0; b < LEN; b++)
+			d |= (uint32_t)(got[i * LEN + b] ^ want[i * LEN + b]);
+		if (d) {
+			cnt++;
+			if (i < lo)
+				lo = i;
+		}
+	}
+	if (cnt) {
+		atomicAdd(&result[0], cnt);
+		atomicMin(&result[1], lo);
+	}
+}
+constexpr uint32_t KID_COMPARE = ECG_KID_CSUM + N_CSUM + N_SPLIT + N_GROUP;
+
 } // namespace
+
+extern "C" int ecg_k_launch_csum_compare(const void *got, const void *want, uint64_t n, uint32_t len,
+					 uint64_t *result, void *stream, uint32_t *kernel_id)
+{
+	uint64_t nb = (n + CS_BLOCK - 1) / CS_BLOCK;
+
+	if (n == 0)
+		return (int)hipSuccess;
+	if (nb > 256 * 4)
+		nb = 256 * 4;
+	void (*fn)(const uint8_t *, const uint8_t *, uint64_t, unsigned long long *) =
+		len == 2 ? ecg_csum_compare_kernel<2> : len == 4 ? ecg_csum_compare_kernel<4>
+		: len == 8 ? ecg_csum_compare_kernel<8> : nullptr;
+	if (fn == nullptr)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL(fn, dim3((uint32_t)nb), dim3(CS_BLOCK), 0, (hipStream_t)stream, (const uint8_t *)got,
+			   (const uint8_t *)want, n, (unsigned long long *)result);
+	if (kernel_id)
+		*kernel_id = KID_COMPARE;
+	return (int)hipGetLastError();
+}
 
 extern "C" const char *ecg_k_csum_kernel_name(uint32_t id)
 {
+	if (id == KID_COMPARE)
+		return "ecg_csum_compare_kernel";
 	if (id >= ECG_KID_CSUM && id < ECG_KID_CSUM + N_CSUM)
 		return g_csum[id - ECG_KID_CSUM].name;
 	if (id >= ECG_KID_CSUM + N_CSUM && id < ECG_KID_CSUM + N_CSUM + N_SPLIT)

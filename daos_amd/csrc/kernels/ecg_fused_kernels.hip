@@ -37,6 +37,11 @@
 #ifndef ECG_FUSED_DEFER
 #define ECG_FUSED_DEFER 2
 #endif
+// the SRC instantiations' register budget: 2 waves per SIMD (<= 256 VGPRs), so
+// that k = 16 with crc64 keeps its 16 source registers out of scratch
+#ifndef ECG_FUSED_WPE_SRC
+#define ECG_FUSED_WPE_SRC 2
+#endif
 
 // Work item `it` of the fused kernel -> chunk c, sub-chunk h, its columns
 // [col0, col1) and the row of Q.kh its threads multiply by (ecg_kabi.h).
@@ -76,6 +81,20 @@ __device__ __forceinline__ const ecg_mm_params_t &kernarg_fresh()
 
 	asm volatile("" : "+s"(p));
 	return *(const ecg_mm_params_t *)p;
+}
+
+// The second kernel argument, re-read the same way: the SRC tail takes its
+// output pointer and slots from here, or all KM slots stay live in SGPRs
+// across the walk.
+typedef __attribute__((address_space(4))) const char kbytes_t;
+typedef __attribute__((address_space(4))) const ecg_mmcs_params_t kqparams_t;
+
+__device__ __forceinline__ const ecg_mmcs_params_t &kernarg_fresh_q()
+{
+	kbytes_t *p = (kbytes_t *)__builtin_amdgcn_kernarg_segment_ptr();
+
+	asm volatile("" : "+s"(p));
+	return *(const ecg_mmcs_params_t *)(kqparams_t *)(p + ((sizeof(ecg_mm_params_t) + 7) & ~(size_t)7));
 }
 
 // A column's outputs waiting to be folded (ECG_FUSED_DEFER): the fold of
@@ -123,12 +142,17 @@ __device__ __forceinline__ void mmcs_fold(const T *s_sl, const T *s_sh, int rows
 
 // DF: 0 fold this column now; 1 fold the pending column and leave this one
 // pending; 2 leave this one pending (nothing pending yet).
+// SRC: the column's source pieces (cur, exactly the cells' bytes: operands are
+// 16-byte aligned) are folded into scrc[j] too, by the rules of the outputs.
+// They are folded in this call, never deferred: cur is the prefetch target
+// of the next call, and a pending copy would cost 4 * KM VGPRs.
 template <int KM, int RM, int W, bool REFL, int TB, bool PF, uint32_t STRIDE, bool FULL, int U, int DF = 0,
-	  typename T>
+	  bool SRC = false, typename T>
 __device__ __forceinline__ void mmcs_col(const ecg_mm_params_t &P0, const u32x4 *s_tbl, const T *s_sl,
 					 const T *s_sh, int k, int rows, uint32_t s, uint64_t cbase, uint64_t next,
 					 uint32_t lo, bool more, bool first, uint64_t init, uint32_t pos, bool gshift,
-					 u32x4 *cur, u32x4 *nxt, T *crc, mmcs_pend<RM> *pd = nullptr)
+					 u32x4 *cur, u32x4 *nxt, T *crc, mmcs_pend<RM> *pd = nullptr,
+					 T *scrc = nullptr)
 {
 	const ecg_mm_params_t &P = kernarg_fresh();	// == P0 (first kernel argument)
 	(void)P0;
@@ -177,6 +201,8 @@ __device__ __forceinline__ void mmcs_col(const ecg_mm_params_t &P0, const u32x4 
 		pd->pos = pos;
 		pd->gshift = gshift;
 	}
+	if constexpr (SRC)
+		mmcs_fold<KM, W, REFL, TB, U>(s_sl, s_sh, k, cur, have, first, init, pos, gshift, scrc);
 }
 
 // Fused product + checksum of every output cell (ecg_kabi.h, ecg_mmcs_params).
@@ -192,8 +218,12 @@ __device__ __forceinline__ void mmcs_col(const ecg_mm_params_t &P0, const u32x4 
 // The outputs are never re-read from HBM: the checksum costs LDS lookups on
 // p/(k+p) of the traffic instead of a second pass over the regenerated
 // cells (ref:src/object/srv_obj_migrate.c:1156 checksums them after encode).
-template <int K, int R, int W, bool REFL, int TB>
-__global__ void __launch_bounds__(BLOCK, ECG_FUSED_WPE(W))
+// SRC (ecg_encode_csum_all / ecg_recover_csum_all): KM more CRC registers
+// hold the checksums of the source cells the product reads, folded from the
+// registers the product consumes -- no HBM traffic, (k + rows) / rows times
+// the lookups.  Finished like the outputs, into Q.src_out.
+template <int K, int R, int W, bool REFL, int TB, bool SRC = false>
+__global__ void __launch_bounds__(BLOCK, SRC ? ECG_FUSED_WPE_SRC : ECG_FUSED_WPE(W))
 ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 {
 	using T = typename ecg_crc::reg<W>::T;
@@ -203,7 +233,9 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 	constexpr int KM = K ? K : ECG_KMAX_K;
 	constexpr int RM = R ? R : ECG_KMAX_R;
 	constexpr bool PF = K != 0 && K <= ECG_FUSED_PF_MAXK && (ECG_FUSED_PF64 || W != 64);	// prefetch: 4*KM more VGPRs
-	constexpr bool DEFER = (ECG_FUSED_DEFER & (W == 64 ? 2 : 1)) != 0;	// fold one column late
+	// fold one column late; not with SRC, whose source folds are already
+	// independent work next to the product and which needs the registers
+	constexpr bool DEFER = !SRC && (ECG_FUSED_DEFER & (W == 64 ? 2 : 1)) != 0;
 	constexpr int T2V = (RM + 3) / 4;
 	constexpr int PER_J = RM + T2V;
 	__shared__ u32x4 s_tbl[KM * PER_J];
@@ -302,6 +334,7 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 			constexpr bool PRE = decltype(pre)::value;
 			uint32_t c, i, col1, khrow;
 			T crc[RM];
+			T scrc[SRC ? KM : 1];
 
 			mmcs_item(Q, it, c, i, col1, khrow);
 			const uint64_t c0 = (uint64_t)c * Q.chunk_bytes;
@@ -319,6 +352,11 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 #pragma unroll
 			for (int r = 0; r < RM; r++)
 				crc[r] = 0;
+			if constexpr (SRC) {
+#pragma unroll
+				for (int j = 0; j < KM; j++)
+					scrc[j] = 0;
+			}
 			// Pipelined pairs of full columns, the prefetch buffers swapping
 			// roles (a register copy xa = xb would wait for the prefetched loads
 			// and serialise the walk); then the rest -- an odd full column, the
@@ -351,28 +389,28 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 				if constexpr (DEFER) {
 					// the first trip peeled: nothing pending at its first column
 					const uint64_t cb = c0 + (uint64_t)i * CHUNK_BYTES;
-					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D2>(
+					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D2, SRC>(
 						P, s_tbl, s_sl, s_sh, k, rows, s, cb, cb + CHUNK_BYTES, lo, true,
-						i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xc, crc, &pd);
-					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1>(
+						i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xc, crc, &pd, scrc);
+					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1, SRC>(
 						P, s_tbl, s_sl, s_sh, k, rows, s, cb + CHUNK_BYTES, cb + 2 * CHUNK_BYTES, lo,
-						i + 2 < iend, false, Q.init, (col1 - 2 - i) % UF, true, xc, xa, crc, &pd);
+						i + 2 < iend, false, Q.init, (col1 - 2 - i) % UF, true, xc, xa, crc, &pd, scrc);
 					i += 2;
 				}
 				for (; i < iend; i += 2) {
 					const uint64_t cb = c0 + (uint64_t)i * CHUNK_BYTES;
-					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1>(
+					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1, SRC>(
 						P, s_tbl, s_sl, s_sh, k, rows, s, cb, cb + CHUNK_BYTES, lo, true,
-						i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xc, crc, &pd);
-					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1>(
+						i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xc, crc, &pd, scrc);
+					mmcs_col<KM, RM, W, REFL, TB, true, CHUNK_BYTES, true, UF, D1, SRC>(
 						P, s_tbl, s_sl, s_sh, k, rows, s, cb + CHUNK_BYTES, cb + 2 * CHUNK_BYTES, lo,
-						i + 2 < iend, false, Q.init, (col1 - 2 - i) % UF, true, xc, xa, crc, &pd);
+						i + 2 < iend, false, Q.init, (col1 - 2 - i) % UF, true, xc, xa, crc, &pd, scrc);
 				}
 			}
 			for (; i < col1; i++)
-				mmcs_col<KM, RM, W, REFL, TB, false, CHUNK_BYTES, false, UF, D1>(
+				mmcs_col<KM, RM, W, REFL, TB, false, CHUNK_BYTES, false, UF, D1, SRC>(
 					P, s_tbl, s_sl, s_sh, k, rows, s, c0 + (uint64_t)i * CHUNK_BYTES, 0, lo, false,
-					i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xa, crc, &pd);
+					i == 0 && threadIdx.x == 0, Q.init, (col1 - 1 - i) % UF, true, xa, xa, crc, &pd, scrc);
 			if constexpr (DEFER) {
 				mmcs_fold<RM, W, REFL, TB, UF>(s_sl, s_sh, rows, pd.v, pd.have, pd.first, Q.init, pd.pos,
 							       pd.gshift, crc);
@@ -424,6 +462,52 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 					}
 				}
 			}
+			// the sources' registers, finished the same way, SB side by side
+			if constexpr (SRC) {
+				constexpr int SB = 4;
+#pragma unroll
+				for (int j0 = 0; j0 < KM; j0 += SB) {
+					T sv[SB];
+#pragma unroll
+					for (int b = 0; b < SB; b++) {
+						sv[b] = 0;
+						if (j0 + b < KM) {
+							if constexpr (REFL)
+								sv[b] = ecg_crc::lane_mul_nib<W>(scrc[j0 + b], s_nibl, s_r4, lane);
+							else
+								sv[b] = ecg_crc::mulmod<W, REFL>(kh[khrow * 256 + threadIdx.x],
+												 scrc[j0 + b], poly);
+						}
+					}
+#pragma unroll
+					for (int b = 0; b < SB; b++)
+						sv[b] = ecg_crc::wave_xor_uniform(sv[b]);
+					if constexpr (REFL) {
+#pragma unroll
+						for (int b = 0; b < SB; b++)
+							sv[b] = ecg_crc::wave_xor_uniform(
+								((sv[b] >> (lane & (uint32_t)(W - 1))) & 1u) ? kbv : (T)0);
+					}
+					if (lane == 0) {
+						const ecg_mmcs_params_t &QF = kernarg_fresh_q();	// == Q
+#pragma unroll
+						for (int b = 0; b < SB; b++) {
+							if (j0 + b < KM && j0 + b < k) {
+								T x = sv[b];
+								if (threadIdx.x == 0 && khrow == (c + 1 == Q.nch ? Q.nh : 0))
+									x ^= (T)Q.xorout;	// once per chunk
+								const uint64_t slot =
+									((uint64_t)QF.src_slot[j0 + b] * P.nstripes + s) * Q.nch + c;
+								if constexpr (W == 16)
+									atomicXor((uint32_t *)QF.src_out + slot / 2,
+										  (uint32_t)x << (16 * (slot & 1)));
+								else
+									atomicXor((T *)QF.src_out + slot, x);
+							}
+						}
+					}
+				}
+			}
 	};
 	// The workgroup's work: items blockIdx.x, blockIdx.x + gridDim.x, ... of
 	// stripe blockIdx.y (+ gridDim.y ...) -- the grid never exceeds the item
@@ -441,6 +525,7 @@ struct csentry {
 	mmcs_fn_t fn;
 	const char *name;
 	int b8;		/* CRC table kind TB of the instantiation */
+	bool src;	/* checksums the source cells too */
 };
 
 /* The table kind TB of each instantiation is the one measured fastest for
@@ -450,14 +535,23 @@ struct csentry {
 #define CS_TB(K_, R_, W_) ((W_) == 64 || ((W_) == 32 && (K_) == 8 && (R_) == 2) ? 1 : 0)
 #define CSE(K_, R_, T_, W_, RF_, N_) \
 	{K_, R_, T_, ecg_mm_csum_kernel<K_, R_, W_, RF_, CS_TB(K_, R_, W_)>, \
-	 "ecg_mm_csum_kernel<" #K_ "," #R_ "," N_ ">", CS_TB(K_, R_, W_)}
+	 "ecg_mm_csum_kernel<" #K_ "," #R_ "," N_ ">", CS_TB(K_, R_, W_), false}
 #define CSE3(K_, R_) CSE(K_, R_, 1, 16, false, "crc16"), CSE(K_, R_, 2, 32, true, "crc32"), \
 		     CSE(K_, R_, 3, 64, true, "crc64")
+/* the SRC instantiations, with the table kind of their plain siblings */
+#define CSS(K_, R_, T_, W_, RF_, N_) \
+	{K_, R_, T_, ecg_mm_csum_kernel<K_, R_, W_, RF_, CS_TB(K_, R_, W_), true>, \
+	 "ecg_mm_csum_kernel<" #K_ "," #R_ "," N_ ",src>", CS_TB(K_, R_, W_), true}
+#define CSS3(K_, R_) CSS(K_, R_, 1, 16, false, "crc16"), CSS(K_, R_, 2, 32, true, "crc32"), \
+		     CSS(K_, R_, 3, 64, true, "crc64")
 
 static const csentry g_cskernels[] = {
 	CSE3(2, 1), CSE3(2, 2), CSE3(2, 3), CSE3(4, 1), CSE3(4, 2), CSE3(4, 3),
 	CSE3(8, 1), CSE3(8, 2), CSE3(8, 3), CSE3(16, 1), CSE3(16, 2), CSE3(16, 3),
 	CSE3(0, 0),
+	CSS3(2, 1), CSS3(2, 2), CSS3(2, 3), CSS3(4, 1), CSS3(4, 2), CSS3(4, 3),
+	CSS3(8, 1), CSS3(8, 2), CSS3(8, 3), CSS3(16, 1), CSS3(16, 2), CSS3(16, 3),
+	CSS3(0, 0),
 };
 #define N_CSKERNELS ((uint32_t)(sizeof(g_cskernels) / sizeof(g_cskernels[0])))
 #define KID_FUSED ECG_KID_FUSED	/* fused kernel ids: KID_FUSED + index */
@@ -472,6 +566,7 @@ extern "C" const char *ecg_k_fused_kernel_name(uint32_t id)
 extern "C" int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs_params_t *q,
 				       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
 {
+	const bool src = q->src_out != nullptr;
 	uint32_t id = N_CSKERNELS;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
@@ -480,19 +575,20 @@ extern "C" int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs
 	    (q->chunk_bytes % CHUNK_BYTES) || q->chunk_bytes == 0)
 		return 1;
 	for (uint32_t i = 0; i < N_CSKERNELS; i++)
-		if (g_cskernels[i].type == (int)q->type && g_cskernels[i].k == (int)p->k &&
-		    g_cskernels[i].r == (int)p->rows) {
+		if (g_cskernels[i].src == src && g_cskernels[i].type == (int)q->type &&
+		    g_cskernels[i].k == (int)p->k && g_cskernels[i].r == (int)p->rows) {
 			id = i;
 			break;
 		}
 	if (id == N_CSKERNELS)
 		for (uint32_t i = 0; i < N_CSKERNELS; i++)
-			if (g_cskernels[i].type == (int)q->type && g_cskernels[i].k == 0) {
+			if (g_cskernels[i].src == src && g_cskernels[i].type == (int)q->type &&
+			    g_cskernels[i].k == 0) {
 				id = i;
 				break;
 			}
 	if (id == N_CSKERNELS)			// no instantiation (not 1: that means "two-pass")
-		return (int)hipErrorInvalidDeviceFunction;
+		return src ? 1 : (int)hipErrorInvalidDeviceFunction;
 	if (q->nitems == 0 || q->ncols == 0 || q->kh == nullptr)
 		return (int)hipErrorInvalidDeviceFunction;
 	// default: ~16 KiB of columns per workgroup (tools/tune8.py,

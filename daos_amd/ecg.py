@@ -184,6 +184,12 @@ _SIGS = [
                                   C.c_int64, C.c_int, C.c_uint64, C.c_uint64, vp, vp]),
     ("ecg_recover_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, u32p, C.c_int,
                                    C.c_int, C.c_uint64, C.c_uint64, vp, vp]),
+    ("ecg_encode_csum_all", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
+                                      C.c_int64, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    ("ecg_recover_csum_all", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, u32p, C.c_int,
+                                       C.c_int, C.c_uint64, C.c_uint64, vp, vp, u32p, vp]),
+    ("ecg_csum_compare", C.c_int, [vp, C.c_int, vp, vp, C.c_uint64, vp, vp]),
+    ("ecg_set_csum_all_route", C.c_int, [vp, C.c_uint32]),
 ]
 
 HASH_CRC16, HASH_CRC32, HASH_CRC64, HASH_ADLER32 = 1, 2, 3, 7
@@ -577,6 +583,33 @@ class Context:
                      err_list: Sequence[int], htype: int, chunksize: int, rec_size: int, csums: int, stream=None):
         _chk(lib().ecg_recover_csum(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride, _u32(err_list),
                                     len(err_list), htype, chunksize, rec_size, csums, stream), "recover_csum")
+
+    def encode_csum_all(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
+                        parity: int, parity_cell_stride: int, parity_stripe_stride: int, htype: int,
+                        chunksize: int, rec_size: int, data_csums: int, parity_csums: int, stream=None):
+        """encode_csum + checksums of the data cells: data_csums[k][S][nch], parity_csums[p][S][nch]."""
+        _chk(lib().ecg_encode_csum_all(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
+                                       parity_cell_stride, parity_stripe_stride, htype, chunksize, rec_size,
+                                       data_csums, parity_csums, stream), "encode_csum_all")
+
+    def recover_csum_all(self, k: int, p: int, cell_bytes: int, nstripes: int, stripes: int, stripe_stride: int,
+                         err_list: Sequence[int], htype: int, chunksize: int, rec_size: int, csums: int,
+                         src_csums: int, stream=None) -> list:
+        """recover_csum + checksums of the k surviving cells it reads, src_csums[k][S][nch];
+        returns src_idx: row i of src_csums is cell src_idx[i] ([] when err_list is empty)."""
+        idx = (C.c_uint32 * k)()
+        _chk(lib().ecg_recover_csum_all(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride,
+                                        _u32(err_list), len(err_list), htype, chunksize, rec_size, csums,
+                                        src_csums, idx, stream), "recover_csum_all")
+        return list(idx) if len(err_list) else []
+
+    def csum_compare(self, htype: int, got: int, want: int, n: int, result: int, stream=None):
+        """Compare n device checksums; result: device memory for two uint64 (mismatches, lowest index)."""
+        _chk(lib().ecg_csum_compare(self.h, htype, got, want, n, result, stream), "csum_compare")
+
+    def set_csum_all_route(self, route: int = 0):
+        """Source checksums of *_csum_all: 0 measured default, 1 fused kernel, 2 two passes."""
+        _chk(lib().ecg_set_csum_all_route(self.h, route), "set_csum_all_route")
 
     def matmul_ptrs(self, k: int, rows: int, coef: np.ndarray, cell_bytes: int, nstripes: int,
                     cells: Sequence[int], stream=None):

@@ -87,6 +87,41 @@ int ecg_recover_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t
 		     void *stripes, int64_t stripe_stride, const uint32_t *err_list, int nerrs,
 		     int type, uint64_t chunksize, uint64_t rec_size, void *csums, void *stream);
 
+/* ecg_encode_csum + checksums of the data cells it reads:
+ * data_csums[k][S][nch], parity_csums[p][S][nch].  What the client's
+ * full-stripe write needs after obj_ec_req_reasb encodes: obj_csum_update
+ * checksums the whole reassembled request (ref:src/object/cli_obj.c:6306).
+ * One kernel (the data pieces are checksummed from the registers the product
+ * reads them into) for the shapes where that was measured faster than two
+ * passes; otherwise ecg_encode_csum followed by ecg_csum_extents over every
+ * data cell, on the stream (ecg_set_csum_all_route). */
+int ecg_encode_csum_all(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			const void *data, int64_t data_stripe_stride, void *parity,
+			int64_t parity_cell_stride, int64_t parity_stripe_stride, int type,
+			uint64_t chunksize, uint64_t rec_size, void *data_csums, void *parity_csums,
+			void *stream);
+
+/* ecg_recover_csum + checksums of the k surviving cells it reads:
+ * src_csums[k][S][nch], row i being cell src_idx[i] of the stripe (src_idx: host array of k
+ * entries, filled before return).  nerrs == 0: returns 0 and touches nothing.
+ * A degraded read compares src_csums with the survivors' stored checksums
+ * (ecg_csum_compare) before it trusts the regenerated cells. */
+int ecg_recover_csum_all(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			 void *stripes, int64_t stripe_stride, const uint32_t *err_list, int nerrs,
+			 int type, uint64_t chunksize, uint64_t rec_size, void *csums, void *src_csums,
+			 uint32_t *src_idx, void *stream);
+
+/* Compare n checksums of ecg_csum_len(type) bytes on the device.  result: device memory for
+ * two uint64 (8-byte aligned) -- the number of mismatches and the lowest mismatching index
+ * (UINT64_MAX if none).  Asynchronous on `stream`. */
+int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want, uint64_t n,
+		     void *result, void *stream);
+
+/* Route of the source checksums of ecg_encode_csum_all / ecg_recover_csum_all:
+ * 0 the measured default per (hash type, k, output rows), 1 the fused kernel
+ * wherever it can take the request, 2 always two passes.  Same results. */
+int ecg_set_csum_all_route(ecg_ctx_t *ctx, uint32_t route);
+
 /* Launch tuning: cap on checksum workgroups (4 chunks in flight each, grid-
  * stride beyond); 0 restores the default. */
 int ecg_set_csum_launch(ecg_ctx_t *ctx, uint32_t max_blocks);
@@ -94,8 +129,9 @@ int ecg_set_csum_launch(ecg_ctx_t *ctx, uint32_t max_blocks);
 /* Launch tuning: 4 KiB columns per work item of the fused product +
  * checksum kernels (ecg_encode_csum / ecg_recover_csum); 0 restores the
  * default (env ECG_FUSED_COLS, else by hash type, k and output rows: 2 for
- * crc32 with k = 8 and two rows, 4 for one row or k >= 8, else 8).  Same
- * results either way. */
+ * crc32 with k = 8 and two rows, 4 for one row or k >= 8, else 8; 8 for the
+ * kernels of ecg_encode_csum_all / ecg_recover_csum_all).  Same results
+ * either way. */
 int ecg_set_fused_cols(ecg_ctx_t *ctx, uint32_t ncols);
 
 #ifdef __cplusplus
