@@ -255,9 +255,60 @@ typedef struct ecg_copy_seg {
 
 #define ECG_KID_COPY_SEGS 900
 
+/*
+ * Parity consistency check (kernels/ecg_verify_kernels.hip, ecg_verify): a
+ * launch computes the syndrome stored_parity[r] ^ XOR_j coef[r][j] * data[j]
+ * of every stripe and folds it into one status word per stripe,
+ *   bits 0-7   row r: the syndrome of parity row r is nonzero somewhere
+ *   bits 8-23  candidate j: data cell j alone explains every nonzero
+ *              syndrome byte seen (s_r = g[r][j] * e for every row r)
+ * preset by the host to no rows and every j < k a candidate; the kernels only
+ * clear candidate bits and set row bits (atomicAnd / atomicOr).
+ * ecg_verify_classify is the one reading of that word, shared by the host's
+ * ecg_verify_cell and the summary kernel: -1 clean, 0..k+p-1 the one cell
+ * that explains it, -2 not attributable to one cell.
+ */
+#ifdef __HIPCC__
+#define ECG_KABI_HD __host__ __device__
+#else
+#define ECG_KABI_HD
+#endif
+static inline ECG_KABI_HD int ecg_verify_classify(uint32_t status, int k, int p)
+{
+	const uint32_t rows = status & 0xffu;
+	const uint32_t cand = (status >> 8) & 0xffffu & ((1u << k) - 1u);
+
+	if (rows == 0)
+		return -1;
+	/* one parity row: row 0 and any data cell are indistinguishable */
+	if (p < 2 || (rows >> p) != 0)
+		return -2;
+	if ((rows & (rows - 1u)) == 0)
+		return k + __builtin_ctz(rows);
+	if (rows == (1u << p) - 1u && cand != 0 && (cand & (cand - 1u)) == 0)
+		return __builtin_ctz(cand);
+	return -2;
+}
+
+#define ECG_KID_VERIFY 800u	/* verify kernel ids start here (below ECG_KID_COPY_SEGS) */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
+/* Syndrome pass of ecg_verify: p->src the data cells, p->dst the stored
+ * parity (read only), p->tbl the parity rows; status[nstripes] preset by the
+ * host on `stream`.  bytewise = 0: the 16-byte lane kernel (every cell
+ * address and stride 16-byte aligned, cell_bytes % 16 == 0); 1: the
+ * byte-granular kernel (any alignment and length).  cfg: grid_x / grid_y and
+ * wg_per_cu as for the product. */
+int ecg_k_launch_verify(const ecg_mm_params_t *p, uint32_t *status, int bytewise,
+			const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
+/* result[0] += bad stripes, result[1] = min(result[1], lowest bad stripe),
+ * result[2] += stripes ecg_verify_classify attributes to one cell, result[3]
+ * += bad stripes it does not; the host presets {0, UINT64_MAX, 0, 0}. */
+int ecg_k_launch_verify_summary(const uint32_t *status, uint32_t nstripes, int k, int p,
+				uint64_t *result, void *stream);
+const char *ecg_k_verify_kernel_name(uint32_t kernel_id);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of

@@ -58,6 +58,9 @@ _SIGS = [
     ("ecg_recover", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, u32p, C.c_int, vp]),
     ("ecg_update", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, u32p, vp, vp, C.c_int64,
                              vp, C.c_int64, C.c_int64, vp]),
+    ("ecg_verify", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
+                             C.c_int64, vp, vp, vp]),
+    ("ecg_verify_cell", C.c_int, [C.c_uint32, C.c_int, C.c_int]),
     ("ecg_matmul_ptrs", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp), vp]),
     ("ecg_update_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), u8p, vp]),
     ("ecg_matmul_host", C.c_int, [vp, C.c_int, C.c_int, C.c_int, u8p, C.POINTER(u8p), C.POINTER(u8p), C.c_uint]),
@@ -387,6 +390,12 @@ def recov_matrix(k: int, p: int, err_list: Sequence[int]):
     return rows.reshape(-1, k)[: len(err_list)], np.array(list(dec), dtype=np.uint32), bool(reused.value)
 
 
+def verify_cell(status: int, k: int, p: int) -> int:
+    """ecg_verify_cell: -1 clean, 0..k+p-1 the one cell that explains a status word of
+    Context.verify, -2 not attributable to one cell."""
+    return lib().ecg_verify_cell(int(status), k, p)
+
+
 # ---------------------------------------------------------------- device side
 class DeviceBuffer:
     def __init__(self, ctx: "Context", nbytes: int):
@@ -565,6 +574,15 @@ class Context:
         _chk(lib().ecg_update(self.h, k, p, cell_bytes, nstripes, len(cell_idx), _u32(cell_idx), old, new,
                               upd_stripe_stride, parity, parity_cell_stride, parity_stripe_stride, stream),
              "update")
+
+    def verify(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
+               parity: int, parity_cell_stride: int, parity_stripe_stride: int, status: int, result: int,
+               stream=None):
+        """ecg_verify: read-only parity check, operands as encode(); status: device memory for
+        nstripes uint32 (rows in bits 0-7, candidate data cells in bits 8-23), result: device
+        memory for four uint64 (bad stripes, lowest bad stripe, attributable, not attributable)."""
+        _chk(lib().ecg_verify(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
+                              parity_cell_stride, parity_stripe_stride, status, result, stream), "verify")
 
     def csum_extents(self, htype: int, chunksize: int, rec_size: int, rx_idx: int, rx_nr: int, buf: int,
                      ext_stride: int, n_ext: int, csums: int, stream=None):

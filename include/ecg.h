@@ -164,6 +164,48 @@ int ecg_update(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
 	       void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
 	       void *stream);
 
+/* Parity consistency check: does the stored parity of every stripe still
+ * match its stored data -- what the EC branch of the object verify path
+ * answers by re-encoding into scratch parity and memcmp
+ * (ref:src/object/obj_verify.c) -- in one read-only pass that also says which
+ * cell of a bad stripe is wrong.  Operands are addressed exactly as in
+ * ecg_encode (client layout and the [S][k+p][C] recovery layout alike);
+ * nothing is written to `data` or `parity`.  k <= 16, p <= 8 (every DAOS EC
+ * class); any alignment and length (16-byte aligned cells of a multiple of
+ * 16 bytes run the 16-byte lane kernel, everything else a byte-granular one).
+ *
+ * status[s] (device, nstripes words) describes stripe s:
+ *   ECG_VERIFY_ROWS  bit r: stored parity row r differs from row r of G*data
+ *                    at some byte
+ *   ECG_VERIFY_CAND  bit j: data cell j being wrong, alone, explains every
+ *                    differing byte seen (the syndrome s_r = parity_r ^
+ *                    (G*data)_r equals g[r][j]*e at each of them; the Cauchy1
+ *                    ratios g[r][j]/g[0][j] differ for every j, so at most one
+ *                    j survives a real single-cell error); every j < k when
+ *                    the stripe is clean
+ * result (device, 4 x uint64, 8-byte aligned) = {bad stripes, lowest bad
+ * stripe index (UINT64_MAX if none), bad stripes attributable to one cell,
+ * bad stripes not attributable}; nstripes == 0 leaves {0, UINT64_MAX, 0, 0}.
+ * Asynchronous on `stream`; status and result are valid once it has drained.
+ *
+ * Location ASSUMES AT MOST ONE WRONG CELL PER STRIPE.  That is inherent in a
+ * distance-(p+1) code: two wrong cells can produce the syndrome of a third,
+ * and with p == 1 a wrong parity row and a wrong data cell cannot be told
+ * apart at all.  Detection (ROWS != 0) holds for up to p wrong cells.  The
+ * located cell is regenerated with ecg_recover. */
+#define ECG_VERIFY_ROWS(st)  ((st) & 0xffu)
+#define ECG_VERIFY_CAND(st)  (((st) >> 8) & 0xffffu)
+int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+	       const void *data, int64_t data_stripe_stride,
+	       const void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+	       uint32_t *status, void *result, void *stream);
+/* Reading of one status word (host only): -1 clean; 0..k+p-1 the single cell
+ * (data j, or parity k+r) that explains it -- one parity row alone differing
+ * is that parity cell, all p rows differing with exactly one candidate is
+ * that data cell; -2 not attributable to one cell (two or more cells wrong,
+ * or p == 1, where a bad stripe never is). */
+int ecg_verify_cell(uint32_t status, int k, int p);
+
 /* ---- host-resident pipeline (PCIe-inclusive) ---------------------------- */
 /* One stripe, ISA-L ec_encode_data calling convention: pointers src[k],
  * dst[rows] (any alignment), `len` bytes each;

@@ -8,6 +8,10 @@ report`).  Needs no GPU.
       instantiations with BASE's (exit 1 on any difference or on scratch in
       a SRC instantiation; SGPRs spilled into VGPR lanes are listed, they
       use no scratch)
+  python tools/fused_resources.py --verify VERIFY.txt [PRODUCT.txt]
+      the ecg_verify kernels (remarks of ecg_verify_kernels.hip), each lane
+      kernel beside its product counterpart from the remarks of
+      ecg_kernels.hip; exit 1 if one uses scratch
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -38,7 +42,61 @@ def parse(path):
     return out
 
 
+VERIFY = re.compile(r"_Z\d+(ecg_verify_(?:byte_|summary_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
+PRODUCT = re.compile(r"_Z13ecg_mm_kernelILi(\d+)ELi(\d+)ELb0ELb0ELi16EE")
+
+
+def parse_named(path, pattern):
+    """{(kernel name, K, R): fields} of the kernels whose mangled name matches `pattern`."""
+    out, cur = {}, None
+    for line in open(path):     # "remark: <file:line:col:> Function Name: ..." with or without the location
+        m = re.search(r"\sFunction Name: (\S+)", line)
+        if m:
+            n = pattern.match(m.group(1))
+            cur = None
+            if n:
+                g = n.groups()
+                cur = (g[0], int(g[1] or -1), int(g[2] or -1)) if len(g) == 3 else ("ecg_mm_kernel", int(g[0]), int(g[1]))
+                out[cur] = {}
+            continue
+        if cur is None:
+            continue
+        for f in FIELDS:
+            m = re.search(r"\s" + re.escape(f) + r": (\d+)", line)
+            if m:
+                out[cur][f] = int(m.group(1))
+    return out
+
+
+def verify_table(verify_txt, product_txt=None):
+    """Table of the ecg_verify kernels (remarks of ecg_verify_kernels.hip); with the
+    remarks of ecg_kernels.hip, each lane kernel's VGPRs / occupancy beside its
+    product counterpart ecg_mm_kernel<K,R,0,0> (16-byte lanes).  Exit 1 on scratch."""
+    ver = parse_named(verify_txt, VERIFY)
+    prod = parse_named(product_txt, PRODUCT) if product_txt else {}
+    bad = 0
+    extra = " product VGPRs | product waves/SIMD |" if prod else ""
+    print("| kernel | " + " | ".join(FIELDS) + " |" + extra)
+    print("|" + "---|" * (1 + len(FIELDS) + (2 if prod else 0)))
+    for key in sorted(ver, key=lambda t: (t[0] != "ecg_verify_kernel", t[0], t[1] == 0, t[1], t[2])):
+        name, k, r = key
+        v = ver[key]
+        label = f"`{name}<{k},{r}>`" if k >= 0 else f"`{name}`"
+        row = f"| {label} | " + " | ".join(str(v.get(f, "")) for f in FIELDS) + " |"
+        if prod:
+            pv = prod.get(("ecg_mm_kernel", k, r), {})
+            row += f" {pv.get('VGPRs', '')} | {pv.get('Occupancy [waves/SIMD]', '')} |"
+        print(row)
+        if v.get("ScratchSize [bytes/lane]") or v.get("VGPRs Spill"):
+            print(f"SCRATCH in {label}", file=sys.stderr)
+            bad = 1
+    print(f"\nverify kernels: {len(ver)}, " + ("SCRATCH USED" if bad else "none uses scratch"))
+    return bad
+
+
 def main():
+    if sys.argv[1] == "--verify":
+        return verify_table(*sys.argv[2:4])
     new = parse(sys.argv[1])
     base = parse(sys.argv[2]) if len(sys.argv) > 2 else None
     bad = 0
