@@ -309,6 +309,28 @@ int ecg_k_launch_verify(const ecg_mm_params_t *p, uint32_t *status, int bytewise
 int ecg_k_launch_verify_summary(const uint32_t *status, uint32_t nstripes, int k, int p,
 				uint64_t *result, void *stream);
 const char *ecg_k_verify_kernel_name(uint32_t kernel_id);
+/* Repair pass of ecg_repair (kernels/ecg_repair_kernels.hip): p as for
+ * ecg_k_launch_verify (src the data cells, dst the parity rows, rows = p;
+ * p->tbl unused), status[nstripes] the words a verify of the same operands
+ * left (read only).  For every stripe ecg_verify_classify attributes to one
+ * cell c, that cell is rewritten with row c of rowtbl: (k + p) x k perm
+ * tables in device memory, row c slot j the coefficient of source j, where
+ * the sources of c >= k are the k data cells and those of c < k the data
+ * cells with slot c replaced by parity row 0 (host/ecg_repair.c
+ * ecg_repair_row).  result[0] += stripes repaired, result[1] = min(result[1],
+ * lowest bad stripe left as it is), result[2] += data cells rewritten,
+ * result[3] += bad stripes left; the host presets {0, UINT64_MAX, 0, 0}.
+ * bytewise as for verify.  cfg: grid_x / grid_y; grid.y runs over groups of
+ * 64 stripes (a block row reads its group's status words with one load) and
+ * by default at most ECG_REPAIR_GRID_X blocks share a group and stride over
+ * a stripe's 4 KiB columns, so a clean batch costs its block count, not its
+ * bytes. */
+#define ECG_REPAIR_GRID_X 64u
+#define ECG_KID_REPAIR 850u	/* repair kernel ids start here (below ECG_KID_COPY_SEGS) */
+int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint32_t *status,
+			uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg, void *stream,
+			uint32_t *kernel_id);
+const char *ecg_k_repair_kernel_name(uint32_t kernel_id);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of

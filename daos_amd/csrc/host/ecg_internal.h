@@ -86,6 +86,10 @@ struct ecg_ctx {
 	hipStream_t dpool[ECG_DROPIN_STREAMS];	/* device-cell drop-in calls (ecg_stage.c) */
 	int ndpool;
 	struct ecg_tuner *tuner;	/* blocks-per-CU cap per shape (ecg_tune.c) */
+	/* device row tables of ecg_repair by (k, p): (k + p) x k ecg_ptbl_t, built
+	 * and uploaded on first use under `lock`, kept until ecg_ctx_destroy
+	 * (ecg_repair.c) */
+	void *repair_tbl[ECG_KMAX_K][ECG_KMAX_R];
 	ecg_stats_t stats;		/* telemetry (ecg_get_stats), updated with atomics */
 };
 
@@ -139,6 +143,9 @@ int ecg_segs_add(struct ecg_segs *v, uint64_t dst, uint64_t src, uint64_t len);
 void ecg_segs_fini(struct ecg_segs *v);
 /* launch over a device copy of v->seg already queued on st */
 int ecg_segs_launch(const struct ecg_segs *v, const void *segs_dev, hipStream_t st);
+
+/* repair row tables (ecg_repair.c) */
+void ecg_repair_ctx_fini(ecg_ctx_t *ctx);
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);

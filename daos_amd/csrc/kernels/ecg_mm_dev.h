@@ -361,6 +361,31 @@ __device__ __forceinline__ void mm_item(const ecg_mm_params_t &P, const u32x4 *t
 	mm_compute<KM, RM, ACC, KEEP, true, G, PH, DIFF>(P, tb, k, rows, s, cbase, lo, x, keep);
 }
 
+// One column of the product over cells given by address (the pointer-table
+// kernel, ecg_ptr_kernels.hip, and the repair kernel, ecg_repair_kernels.hip):
+// a[j] = the wave-uniform address of input cell j at this column (j < k),
+// a[KM + r] that of output row r.
+template <int KM, int RM, int G>
+__device__ __forceinline__ void mm_ptr_item(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
+					    uint32_t s, uint64_t cbase, uint32_t lo, const uint64_t *a)
+{
+	// phased loads as the offset kernel's (ECG_MM_PHASE): the first PH cells
+	// now, the rest as the fold reaches them
+	constexpr int PH = (ECG_MM_PHASE(KM, G) > 0 && ECG_MM_PHASE(KM, G) < KM && KM % ECG_MM_PHASE(KM, G) == 0)
+				   ? ECG_MM_PHASE(KM, G) : 0;
+	u32x4 x[KM], outv[RM];
+
+#pragma unroll
+	for (int j = 0; j < (PH ? PH : KM); j++)
+		if (j < k)
+			x[j] = ld_src<G>(reinterpret_cast<const uint8_t *>(a[j]), lo);
+	mm_compute<KM, RM, false, true, false, G, PH, false, true>(P, tb, k, rows, s, cbase, lo, x, outv, a);
+#pragma unroll
+	for (int r = 0; r < RM; r++)
+		if (r < rows)
+			st_g<G>(reinterpret_cast<uint8_t *>(a[KM + r]) + lo, outv[r]);
+}
+
 // One dword of every output row at byte offset `off` of the cells (the
 // partial last column of a G = 4 / 1 launch: the dword lies inside the cell).
 // The k loads are issued together.  Cells off a dword boundary (G = 1, and

@@ -21,26 +21,7 @@
 #include "../ecg_kabi.h"
 #include "ecg_mm_dev.h"
 
-template <int KM, int RM, int G>
-__device__ __forceinline__ void mm_ptr_item(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
-					    uint32_t s, uint64_t cbase, uint32_t lo, const uint64_t *a)
-{
-	// phased loads as the offset kernel's (ECG_MM_PHASE): the first PH cells
-	// now, the rest as the fold reaches them
-	constexpr int PH = (ECG_MM_PHASE(KM, G) > 0 && ECG_MM_PHASE(KM, G) < KM && KM % ECG_MM_PHASE(KM, G) == 0)
-				   ? ECG_MM_PHASE(KM, G) : 0;
-	u32x4 x[KM], outv[RM];
-
-#pragma unroll
-	for (int j = 0; j < (PH ? PH : KM); j++)
-		if (j < k)
-			x[j] = ld_src<G>(reinterpret_cast<const uint8_t *>(a[j]), lo);
-	mm_compute<KM, RM, false, true, false, G, PH, false, true>(P, tb, k, rows, s, cbase, lo, x, outv, a);
-#pragma unroll
-	for (int r = 0; r < RM; r++)
-		if (r < rows)
-			st_g<G>(reinterpret_cast<uint8_t *>(a[KM + r]) + lo, outv[r]);
-}
+// (the column code, mm_ptr_item, is shared with the repair kernel: ecg_mm_dev.h)
 
 // The partial last column of the G = 4 / 1 kernels, at column offset `off`
 // of every cell: one dword (nb = 4; misaligned cells read and written as they

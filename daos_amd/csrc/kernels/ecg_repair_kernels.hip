@@ -1,0 +1,265 @@
+// ecg_repair_kernels.hip -- rewrite the cell ecg_verify located (ecg_repair):
+// the second half of a scrub, queued behind the check on the same stream with
+// no host round trip in between.
+//
+// A block row takes a group of 64 stripes: lane l of every wave reads the
+// status word of the group's stripe l (one coalesced load), classifies it
+// with the one reading of that word the host and the summary kernel share
+// (ecg_kabi.h ecg_verify_classify), and a ballot leaves the located stripes
+// as a wave-uniform 64-bit mask -- in a batch that is almost always clean it
+// is zero and the block is done.  The block walks the set bits; for a located
+// cell c it chooses its decode row and its operands per stripe:
+//   c >= k  parity row c-k = row c-k of G over the k data cells
+//   c <  k  data cell c = the decode row of erasure {c}: the other k-1 data
+//           cells in their own slots, parity row 0 in slot c
+// i.e. k source addresses and one destination built in registers from the
+// strided operands, the k perm tables of row c staged into LDS from the
+// (k+p) x k row tables the host keeps on the device (host/ecg_repair.c), and
+// the product's column code with one output row (ecg_mm_dev.h mm_ptr_item,
+// the pointer-table kernel's).  Every address derives from the classified c
+// alone, never from raw status bits, so any of the 2^32 status values is
+// safe; the destination is never one of its own sources, so the in-place
+// write has no hazard.
+//
+// The grid is not one block per (column, stripe), nor one block row per
+// stripe: grid.y runs over the groups of 64 stripes and grid.x over at most
+// ECG_REPAIR_GRID_X columns (blocks stride over the rest), so a clean batch
+// costs ECG_REPAIR_GRID_X * S / 64 blocks of one load each whatever the cell
+// size, and a bad stripe still has ECG_REPAIR_GRID_X blocks to itself.
+// Column-block 0 of a group counts its bad stripes into `result` (one atomic
+// per repaired or left-as-it-is bad stripe, issued by the stripe's lane).
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../ecg_kabi.h"
+#include "ecg_mm_dev.h"
+
+namespace {
+
+// result {stripes repaired, lowest bad stripe left, data cells rewritten, bad
+// stripes left} for stripe s classified c (c != -1); one thread per stripe
+__device__ __forceinline__ void repair_count(unsigned long long *result, uint32_t s, int c, int k)
+{
+	if (c >= 0) {
+		atomicAdd(&result[0], 1ull);
+		if (c < k)
+			atomicAdd(&result[2], 1ull);
+	} else {
+		atomicMin(&result[1], (unsigned long long)s);
+		atomicAdd(&result[3], 1ull);
+	}
+}
+
+#define REPAIR_GROUP 64u	// stripes per block row: one status word per lane
+
+// The group's status words: *cl = this lane's reading of stripe g * 64 + lane
+// (-1 past the batch), returned the mask of the stripes to repair -- the same
+// in every wave of the block, the words being read-only for the launch.
+__device__ __forceinline__ uint64_t repair_scan(const uint32_t *__restrict__ status, uint32_t nstripes, uint32_t g,
+						int k, int p, unsigned long long *result, int *cl)
+{
+	const uint64_t s = (uint64_t)g * REPAIR_GROUP + (threadIdx.x & 63u);
+	int c = -1;
+
+	if (s < nstripes)
+		c = ecg_verify_classify(status[s], k, p);
+	if (blockIdx.x == 0 && threadIdx.x < 64 && c != -1)
+		repair_count(result, (uint32_t)s, c, k);
+	*cl = c;
+	return __ballot(c >= 0 && c < k + p);	// the second test cannot fail (classify masks)
+}
+
+} // namespace
+
+// K as ecg_mm_kernel's (0 = runtime-shaped), one output row.  16-byte lanes
+// only: every cell address and stride 16-byte aligned, C % 16 == 0 (the
+// launcher sends everything else to the byte kernel), so a partial last
+// column is a lane mask.  P as ecg_verify's: src the data cells, dst the
+// parity rows (dst_cell_off[r] = r * parity_cell_stride), rows = p.
+template <int K>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, 1, 16) ? ECG_MM_WPE(K, 1, 16) : 1)
+ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+		  const uint32_t *__restrict__ status, unsigned long long *result)
+{
+	constexpr int KM = K ? K : ECG_KMAX_K;
+	constexpr int PER_J = 2;	// RM + T2V of one output row
+	__shared__ u32x4 s_tbl[KM * PER_J];
+	const int k = K ? K : (int)P.k;
+	const int p = (int)P.rows;
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const uint32_t lo = lane_off<16>();
+	const uint32_t ngroup = P.nstripes / REPAIR_GROUP + (P.nstripes % REPAIR_GROUP != 0);
+	int staged = -1;	// the row whose tables s_tbl holds
+
+	for (uint32_t g = blockIdx.y; g < ngroup; g += gridDim.y) {
+		int cl;
+		uint64_t todo = repair_scan(status, P.nstripes, g, k, p, result, &cl);
+
+		while (todo) {
+			const int l = __ffsll((unsigned long long)todo) - 1;
+			const int c = __builtin_amdgcn_readlane(cl, l);
+			const uint32_t s = g * REPAIR_GROUP + (uint32_t)l;
+
+			todo &= todo - 1;
+			if (staged != c) {
+				__syncthreads();	// the previous stripe's columns are done with s_tbl
+				if ((int)threadIdx.x < k) {
+					const ecg_ptbl_t t = rowtbl[c * k + (int)threadIdx.x];
+
+					s_tbl[threadIdx.x * PER_J] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
+					s_tbl[threadIdx.x * PER_J + 1] = (u32x4){t.t2, 0u, 0u, 0u};
+				}
+				__syncthreads();
+				staged = c;
+			}
+
+			// the stripe's k sources and its destination (wave-uniform)
+			const uint64_t sb = (uint64_t)(uintptr_t)P.src + (uint64_t)((int64_t)s * P.src_stripe_stride);
+			const uint64_t pb = (uint64_t)(uintptr_t)P.dst + (uint64_t)((int64_t)s * P.dst_stripe_stride);
+			const uint64_t par0 = pb + (uint64_t)P.dst_cell_off[0];
+			uint64_t base[KM + 1];
+
+#pragma unroll
+			for (int j = 0; j < KM; j++)
+				if (j < k)
+					base[j] = j == c ? par0 : sb + (uint64_t)P.src_cell_off[j];
+			base[KM] = c < k ? sb + (uint64_t)c * C : pb + (uint64_t)P.dst_cell_off[c - k];
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+				uint64_t a[KM + 1];
+				uint32_t z = 0;
+
+#pragma unroll
+				for (int j = 0; j < KM + 1; j++) {
+					if (j < k || j == KM) {
+						a[j] = base[j] + cbase;
+						asm volatile("" : "+s"(a[j]));
+					}
+				}
+				asm volatile("" : "+v"(z));
+				const u32x4 *tb = s_tbl + z;
+				// a partial last column is a lane mask (C % 16 == 0 here)
+				if (cbase + CHUNK_BYTES <= C || cbase + lo + 16 <= C)
+					mm_ptr_item<KM, 1, 16>(P, tb, k, 1, s, cbase, lo, a);
+			}
+		}
+	}
+}
+
+// Any alignment, any length: a block takes 4 KiB columns of one stripe at a
+// time, a lane the bytes t, t + 256, ... of a column.  Same status scan,
+// operands, rows and counters as the lane kernel; the row's tables are read
+// where they lie (wave-uniform loads).
+__global__ void __launch_bounds__(BLOCK)
+ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+		       const uint32_t *__restrict__ status, unsigned long long *result)
+{
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const int k = (int)P.k, p = (int)P.rows;
+	const uint32_t ngroup = P.nstripes / REPAIR_GROUP + (P.nstripes % REPAIR_GROUP != 0);
+
+	for (uint32_t g = blockIdx.y; g < ngroup; g += gridDim.y) {
+		int cl;
+		uint64_t todo = repair_scan(status, P.nstripes, g, k, p, result, &cl);
+
+		while (todo) {
+			const int l = __ffsll((unsigned long long)todo) - 1;
+			const int c = __builtin_amdgcn_readlane(cl, l);
+			const uint32_t s = g * REPAIR_GROUP + (uint32_t)l;
+
+			todo &= todo - 1;
+			const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride;
+			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
+			const uint8_t *par0 = pb + P.dst_cell_off[0];
+			const ecg_ptbl_t *row = rowtbl + c * k;
+			uint8_t *dst = c < k ? const_cast<uint8_t *>(sb) + (uint64_t)c * C : pb + P.dst_cell_off[c - k];
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+
+				for (uint64_t i = cbase + threadIdx.x; i < cbase + CHUNK_BYTES && i < C; i += BLOCK) {
+					uint32_t o = 0;
+
+					for (int j = 0; j < k; j++) {
+						const uint8_t *src = j == c ? par0 : sb + P.src_cell_off[j];
+
+						o ^= gf_mul1(row[j], src[i]);
+					}
+					dst[i] = (uint8_t)o;
+				}
+			}
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
+// Dispatch
+// ---------------------------------------------------------------------------
+typedef void (*repair_fn_t)(const ecg_mm_params_t, const ecg_ptbl_t *, const uint32_t *, unsigned long long *);
+
+struct rentry {
+	int k;
+	repair_fn_t fn;
+	const char *name;
+};
+
+#define RE(K_) {K_, ecg_repair_kernel<K_>, "ecg_repair_kernel<" #K_ ">"}
+
+// the k of the DAOS EC classes; the rest runtime-shaped
+static const rentry g_repair[] = {RE(2), RE(4), RE(8), RE(16), RE(0)};
+#define N_REPAIR ((uint32_t)(sizeof(g_repair) / sizeof(g_repair[0])))
+#define KID_REPAIR_BYTE (ECG_KID_REPAIR + N_REPAIR)
+
+extern "C" const char *ecg_k_repair_kernel_name(uint32_t id)
+{
+	if (id >= ECG_KID_REPAIR && id < ECG_KID_REPAIR + N_REPAIR)
+		return g_repair[id - ECG_KID_REPAIR].name;
+	if (id == KID_REPAIR_BYTE)
+		return "ecg_repair_byte_kernel";
+	return "?";
+}
+
+extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint32_t *status,
+				   uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg, void *stream,
+				   uint32_t *kernel_id)
+{
+	hipStream_t st = (hipStream_t)stream;
+	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+
+	if (p->nstripes == 0 || p->cell_bytes == 0)
+		return (int)hipSuccess;
+	if (p->k == 0 || p->k > ECG_KMAX_K || p->rows == 0 || p->rows > ECG_KMAX_R || rowtbl == nullptr ||
+	    status == nullptr || result == nullptr)
+		return (int)hipErrorInvalidValue;
+	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x
+					       : (uint32_t)(nchunk < ECG_REPAIR_GRID_X ? nchunk : ECG_REPAIR_GRID_X);
+	const uint32_t ngroup = p->nstripes / REPAIR_GROUP + (p->nstripes % REPAIR_GROUP != 0);
+	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (ngroup < 65535 ? ngroup : 65535);
+
+	if (bytewise) {
+		hipLaunchKernelGGL(ecg_repair_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
+				   (unsigned long long *)result);
+		if (kernel_id)
+			*kernel_id = KID_REPAIR_BYTE;
+		return (int)hipGetLastError();
+	}
+	// the lane kernel reads and writes dwordx4 at the cells' own addresses
+	if (!aligned16(p) || p->cell_bytes % 16u)
+		return (int)hipErrorInvalidValue;
+
+	uint32_t id = N_REPAIR - 1;	// <0>
+	for (uint32_t i = 0; i < N_REPAIR; i++)
+		if (g_repair[i].k == (int)p->k) {
+			id = i;
+			break;
+		}
+	hipLaunchKernelGGL(g_repair[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
+			   (unsigned long long *)result);
+	if (kernel_id)
+		*kernel_id = ECG_KID_REPAIR + id;
+	return (int)hipGetLastError();
+}

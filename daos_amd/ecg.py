@@ -61,6 +61,9 @@ _SIGS = [
     ("ecg_verify", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_verify_cell", C.c_int, [C.c_uint32, C.c_int, C.c_int]),
+    ("ecg_repair", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
+                             C.c_int64, vp, vp, vp]),
+    ("ecg_repair_row", C.c_int, [C.c_int, C.c_int, C.c_int, u8p, u32p]),
     ("ecg_matmul_ptrs", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp), vp]),
     ("ecg_update_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), u8p, vp]),
     ("ecg_matmul_host", C.c_int, [vp, C.c_int, C.c_int, C.c_int, u8p, C.POINTER(u8p), C.POINTER(u8p), C.c_uint]),
@@ -396,6 +399,15 @@ def verify_cell(status: int, k: int, p: int) -> int:
     return lib().ecg_verify_cell(int(status), k, p)
 
 
+def repair_row(k: int, p: int, cell: int):
+    """ecg_repair_row: the row Context.repair applies for `cell` -> (coef [k], src_idx [k], the
+    logical cells 0..k+p-1 it reads)."""
+    coef = np.zeros(max(1, k), dtype=np.uint8)
+    idx = (C.c_uint32 * max(1, k))()
+    _chk(lib().ecg_repair_row(k, p, cell, _u8(coef), idx), "repair_row")
+    return coef[:k], np.array(list(idx)[:k], dtype=np.uint32)
+
+
 # ---------------------------------------------------------------- device side
 class DeviceBuffer:
     def __init__(self, ctx: "Context", nbytes: int):
@@ -583,6 +595,16 @@ class Context:
         memory for four uint64 (bad stripes, lowest bad stripe, attributable, not attributable)."""
         _chk(lib().ecg_verify(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
                               parity_cell_stride, parity_stripe_stride, status, result, stream), "verify")
+
+    def repair(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
+               parity: int, parity_cell_stride: int, parity_stripe_stride: int, status: int, result: int,
+               stream=None):
+        """ecg_repair: rewrite the one cell verify() located in each bad stripe, operands as
+        verify(); status: the words that verify() left (read only), result: device memory for
+        four uint64 (stripes repaired, lowest bad stripe left, data cells rewritten, bad stripes
+        left).  Queued behind verify() on the same stream it needs no sync in between."""
+        _chk(lib().ecg_repair(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
+                              parity_cell_stride, parity_stripe_stride, status, result, stream), "repair")
 
     def csum_extents(self, htype: int, chunksize: int, rec_size: int, rx_idx: int, rx_nr: int, buf: int,
                      ext_stride: int, n_ext: int, csums: int, stream=None):

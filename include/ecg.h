@@ -192,7 +192,8 @@ int ecg_update(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
  * distance-(p+1) code: two wrong cells can produce the syndrome of a third,
  * and with p == 1 a wrong parity row and a wrong data cell cannot be told
  * apart at all.  Detection (ROWS != 0) holds for up to p wrong cells.  The
- * located cell is regenerated with ecg_recover. */
+ * located cells are rewritten by ecg_repair (below), queued behind this call
+ * on the same stream: the status words never leave the device. */
 #define ECG_VERIFY_ROWS(st)  ((st) & 0xffu)
 #define ECG_VERIFY_CAND(st)  (((st) >> 8) & 0xffffu)
 int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
@@ -205,6 +206,51 @@ int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
  * that data cell; -2 not attributable to one cell (two or more cells wrong,
  * or p == 1, where a bad stripe never is). */
 int ecg_verify_cell(uint32_t status, int k, int p);
+
+/* Repair the stripes ecg_verify found bad and attributed to one cell -- the
+ * second half of a scrub (the object verify path and the checksum scrubber):
+ * ecg_verify, then ecg_repair, two asynchronous calls on one stream.
+ * Operands addressed exactly as in ecg_verify / ecg_encode (client layout and
+ * [S][k+p][C] alike).  status: the nstripes words an ecg_verify of the same
+ * operands left (device, read only; it may not overlap the cells).  For
+ * stripe s with c = ecg_verify_cell(status[s], k, p):
+ *   c == -1 or -2   the stripe is not touched
+ *   c >= k          parity row c-k  = row c-k of G * data
+ *   c <  k          data cell c     = the decode row of erasure {c} over the
+ *                   other k-1 data cells and parity row 0
+ * i.e. byte for byte what ecg_recover(err_list = {c}, nerrs = 1) writes for
+ * that one stripe, and nothing else is written.  Any status value is safe:
+ * candidate bits at or above k and row bits at or above p classify as -2.
+ * result (device, 4 x uint64, 8-byte aligned) = {stripes repaired, lowest bad
+ * stripe left as it is (UINT64_MAX if none), data cells rewritten, bad stripes
+ * left as they are}; nstripes == 0 or cell_bytes == 0 leaves {0, UINT64_MAX,
+ * 0, 0}.  k <= 16, p <= 8; any alignment and length (16-byte aligned cells of
+ * a multiple of 16 bytes run the 16-byte lane kernel, everything else a
+ * byte-granular one).  The cost follows the number of bad stripes, not the
+ * size of the batch.
+ * Asynchronous on `stream`; queued behind the ecg_verify that wrote status it
+ * needs no synchronisation in between.  status is never modified: run
+ * ecg_verify again to confirm the repair.
+ *
+ * The caveats are ecg_verify's.  Location ASSUMES ONE WRONG CELL PER STRIPE.
+ * With p == 1 nothing is ever attributable, so ecg_repair is a valid call
+ * that repairs nothing.  With two or more wrong cells in a stripe a
+ * distance-(p+1) code can MISCORRECT: the syndrome may be that of some third
+ * cell, which is then rewritten to a different valid codeword (and the
+ * second ecg_verify reports the stripe clean).  Callers who keep chunk
+ * checksums (ecg_csum.h) should treat those as the authority. */
+int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+	       void *data, int64_t data_stripe_stride,
+	       void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+	       const uint32_t *status, void *result, void *stream);
+/* The row ecg_repair applies for `cell` (host only, no device needed): coef[k]
+ * and src_idx[k], the logical cells (0..k+p-1) it reads.  cell >= k: the
+ * Cauchy1 parity row over cells 0..k-1.  cell < k: slot i != cell reads data
+ * cell i with g[0][i]/g[0][cell], slot `cell` reads parity row 0 (logical k)
+ * with 1/g[0][cell] -- the coefficients and survivors of ecg_recov_matrix for
+ * err_list = {cell}, which lists them in ascending cell order.
+ * -ECG_DER_INVAL outside 0..k+p-1 or k/p out of range (k <= 16, p <= 8). */
+int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_idx);
 
 /* ---- host-resident pipeline (PCIe-inclusive) ---------------------------- */
 /* One stripe, ISA-L ec_encode_data calling convention: pointers src[k],

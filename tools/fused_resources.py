@@ -12,6 +12,12 @@ report`).  Needs no GPU.
       the ecg_verify kernels (remarks of ecg_verify_kernels.hip), each lane
       kernel beside its product counterpart from the remarks of
       ecg_kernels.hip; exit 1 if one uses scratch
+  python tools/fused_resources.py --repair REPAIR.txt [NEW.txt BASE.txt]...
+      the ecg_repair kernels (remarks of ecg_repair_kernels.hip); exit 1 if
+      one uses scratch.  Each NEW BASE pair after it: the remarks of one
+      other kernel file from this tree and from the tree before, every
+      kernel of which must show identical figures (mm_ptr_item moved into
+      ecg_mm_dev.h; exit 1 on any difference)
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -94,9 +100,41 @@ def verify_table(verify_txt, product_txt=None):
     return bad
 
 
+REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
+ANY = re.compile(r"(\S+)()()")
+
+
+def repair_table(repair_txt, *pairs):
+    """Table of the ecg_repair kernels (remarks of ecg_repair_kernels.hip), exit 1 on scratch;
+    then every kernel of each (new, base) pair of remarks files compared field by field."""
+    rep = parse_named(repair_txt, REPAIR)
+    bad = 0
+    print("| kernel | " + " | ".join(FIELDS) + " |")
+    print("|" + "---|" * (1 + len(FIELDS)))
+    for key in sorted(rep, key=lambda t: (t[0] != "ecg_repair_kernel", t[1] == 0, t[1])):
+        name, k, _ = key
+        v = rep[key]
+        label = f"`{name}<{k}>`" if k >= 0 else f"`{name}`"
+        print(f"| {label} | " + " | ".join(str(v.get(f, "")) for f in FIELDS) + " |")
+        if v.get("ScratchSize [bytes/lane]") or v.get("VGPRs Spill"):
+            print(f"SCRATCH in {label}", file=sys.stderr)
+            bad = 1
+    print(f"\nrepair kernels: {len(rep)}, " + ("SCRATCH USED" if bad else "none uses scratch"))
+    for new_txt, base_txt in zip(pairs[0::2], pairs[1::2]):
+        new, base = parse_named(new_txt, ANY), parse_named(base_txt, ANY)
+        diff = [key[0] for key in sorted(set(new) | set(base)) if new.get(key) != base.get(key)]
+        for name in diff:
+            print(f"DIFF {name}: base {base.get((name, -1, -1))} new {new.get((name, -1, -1))}", file=sys.stderr)
+        bad |= bool(diff)
+        print(f"{new_txt}: {len(new)} kernels compared with {base_txt}, " + ("DIFFERENT" if diff else "identical"))
+    return bad
+
+
 def main():
     if sys.argv[1] == "--verify":
         return verify_table(*sys.argv[2:4])
+    if sys.argv[1] == "--repair":
+        return repair_table(*sys.argv[2:])
     new = parse(sys.argv[1])
     base = parse(sys.argv[2]) if len(sys.argv) > 2 else None
     bad = 0
