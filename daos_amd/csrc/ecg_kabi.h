@@ -331,6 +331,106 @@ int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, cons
 			uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg, void *stream,
 			uint32_t *kernel_id);
 const char *ecg_k_repair_kernel_name(uint32_t kernel_id);
+#ifdef __cplusplus
+}
+#endif
+
+/*
+ * Per-stripe erasure sets (kernels/ecg_recover_masks_kernels.hip,
+ * ecg_recover_masks): bit c of a stripe's mask word = logical cell c is
+ * erased.  The nonempty sets of at most p of the k + p cells are numbered by
+ * size, then by combinatorial rank: the set c1 < c2 < .. < ce has index
+ *   sum_{i<e} C(k+p, i)  +  C(c1, 1) + C(c2, 2) + .. + C(ce, e)
+ * a bijection onto 0 .. N-1, N = sum_{e=1..p} C(k+p, e) (1159 for k = 16,
+ * p = 3).  ecg_erasure_set_read is the one reading of a mask word, shared by
+ * the host's ecg_erasure_set_index and the kernels: the index, ECG_RM_NONE for
+ * mask 0, ECG_RM_LOSS for more than p bits, ECG_RM_RANGE for a bit at or above
+ * k + p -- the kernels leave a stripe of the last two as it is and count it.
+ */
+#define ECG_RM_MAX_K 16
+#define ECG_RM_MAX_P 3
+#define ECG_RM_NONE (-1)
+#define ECG_RM_LOSS (-2)
+#define ECG_RM_RANGE (-3)
+/* C(n, e) for e <= 3 (n < 20 here) */
+static inline ECG_KABI_HD uint32_t ecg_rm_binom(uint32_t n, uint32_t e)
+{
+	return e == 0 ? 1u : e == 1 ? n : e == 2 ? n * (n - 1u) / 2u : n * (n - 1u) * (n - 2u) / 6u;
+}
+/* 1 <= k <= ECG_RM_MAX_K, 1 <= p <= ECG_RM_MAX_P (the callers check) */
+static inline ECG_KABI_HD uint32_t ecg_erasure_set_count(int k, int p)
+{
+	uint32_t n = 0;
+
+	for (int e = 1; e <= p; e++)
+		n += ecg_rm_binom((uint32_t)(k + p), (uint32_t)e);
+	return n;
+}
+static inline ECG_KABI_HD int ecg_erasure_set_read(uint32_t mask, int k, int p)
+{
+	const int e = __builtin_popcount(mask);
+	uint32_t idx = 0, m = mask;
+
+	if (mask == 0)
+		return ECG_RM_NONE;
+	if ((mask >> (k + p)) != 0)	/* k + p <= 19 */
+		return ECG_RM_RANGE;
+	if (e > p)
+		return ECG_RM_LOSS;
+	for (int i = 1; i < e; i++)
+		idx += ecg_rm_binom((uint32_t)(k + p), (uint32_t)i);
+	for (int i = 1; i <= e; i++) {
+		idx += ecg_rm_binom((uint32_t)__builtin_ctz(m), (uint32_t)i);
+		m &= m - 1u;
+	}
+	return (int)idx;
+}
+/*
+ * The set table of one (k, p), device memory, built by host/
+ * ecg_recover_masks.c: entry i (the set of index i) is ECG_RM_ENT_Q(k, p)
+ * 16-byte words,
+ *   word 0      {e, out_idx[0], out_idx[1], out_idx[2]}: the erased cells in the
+ *               order ecg_recov_rows writes them (unused slots 0)
+ *   word 1      dec_idx[j] in byte j: the k survivors the rows read
+ *   words 2..   the e x k perm tables in the product's LDS layout for RM = p
+ *               output rows (ecg_mm_dev.h mm_compute: PER_J = p + 1 words per
+ *               source j -- row r's {t0lo, t0hi, t1lo, t1hi} in word j*PER_J + r,
+ *               its t2 in dword r of word j*PER_J + p), rows >= e zero
+ * so a block stages a set with one 16-byte copy per thread.
+ */
+#define ECG_RM_ENT_Q(k, p) (2u + (uint32_t)(k) * ((uint32_t)(p) + 1u))
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+/* ecg_recover_masks: p->src = p->dst = the stripes ([S][k+p][C], stripe stride
+ * p->src_stripe_stride), p->k, p->rows = p, cell_bytes, nstripes; the cell
+ * offsets and p->tbl are unused.  For every stripe whose mask reads as a set,
+ * the set's e rows are applied to its dec_idx cells and written to its out_idx
+ * cells.  result[0] += stripes recovered, result[1] = min(result[1], lowest
+ * stripe left unrecoverable), result[2] += cells regenerated, result[3] +=
+ * stripes left unrecoverable; the host presets {0, UINT64_MAX, 0, 0}.
+ * bytewise as for verify.  A block row takes `grp` consecutive stripes (1 ..
+ * 64: their mask words are one load and a ballot) and at most grid_x blocks
+ * share them and stride over a stripe's 4 KiB columns.  sparse = 0: grp =
+ * ECG_RM_DENSE_GRP and a block per column up to ECG_RM_DENSE_GRID_X (every
+ * stripe has work: the product's grid); 1: grp = 64 and at most
+ * ECG_REPAIR_GRID_X column blocks (few stripes have work: a clean batch costs
+ * S / 64 * grid_x blocks of one load each).  cfg: grid_x / grid_y override
+ * either. */
+#define ECG_RM_DENSE_GRP 1u
+#define ECG_RM_DENSE_GRID_X 256u
+#define ECG_KID_RECOVER_MASKS 870u	/* ids of the recover_masks kernels start here (below ECG_KID_COPY_SEGS) */
+int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint32_t *masks,
+			       uint64_t *result, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
+			       void *stream, uint32_t *kernel_id);
+const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
+/* ecg_csum_mask (kernels/ecg_csum_kernels.hip): masks[s] |= 1u << (first_cell
+ * + i) when any of the nch checksums of len (2, 4 or 8) bytes at index
+ * s*stripe_stride + i*cell_stride + c differs between got and want. */
+int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
+			   uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride, uint32_t first_cell,
+			   uint32_t len, uint32_t *masks, void *stream, uint32_t *kernel_id);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of

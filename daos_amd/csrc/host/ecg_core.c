@@ -171,6 +171,7 @@ void ecg_ctx_destroy(ecg_ctx_t *ctx)
 	ecg_scratch_free(ctx);
 	ecg_csum_ctx_fini(ctx);
 	ecg_repair_ctx_fini(ctx);
+	ecg_recover_masks_ctx_fini(ctx);
 	ecg_tune_fini(ctx);
 	for (int i = 0; i < ctx->ndpool; i++) {
 		(void)hipStreamSynchronize(ctx->dpool[i]);

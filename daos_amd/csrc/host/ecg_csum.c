@@ -756,6 +756,40 @@ int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want
 	return 0;
 }
 
+int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
+		  uint32_t nstripes, uint32_t ncells, uint32_t nch,
+		  uint64_t stripe_stride, uint64_t cell_stride,
+		  uint32_t first_cell, uint32_t *masks, void *stream)
+{
+	const int cl = ecg_csum_len(type);
+	uint32_t kid = 0;
+	int rc, e;
+
+	if (cl != 2 && cl != 4 && cl != 8)
+		return ecg_fail(-ECG_DER_INVAL, "csum_mask: hash type %d has no 2, 4 or 8 byte checksum", type);
+	if ((uint64_t)first_cell + ncells > 32)
+		return ecg_fail(-ECG_DER_INVAL, "csum_mask: first_cell %u + ncells %u > 32 mask bits", first_cell,
+				ncells);
+	if (masks == NULL || (uintptr_t)masks % 4u)
+		return ecg_fail(-ECG_DER_INVAL, "csum_mask: masks must be 4-byte aligned device memory");
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_mask: NULL context");
+	if (nstripes && ncells && nch && (got == NULL || want == NULL))
+		return ecg_fail(-ECG_DER_INVAL, "csum_mask: NULL checksums");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	if (nstripes == 0 || ncells == 0 || nch == 0)
+		return 0;
+	e = ecg_k_launch_csum_mask(got, want, nstripes, ncells, nch, stripe_stride, cell_stride, first_cell,
+				   (uint32_t)cl, masks, (void *)ecg_pick_stream(ctx, stream), &kid);
+	if (e != 0)
+		return ecg_hip_fail((hipError_t)e, "csum_mask kernel launch");
+	ECG_STAT_ADD(ctx, launches, 1);
+	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	return 0;
+}
+
 /* Fused product + checksum parameters (ecg_kabi.h) for output cells of C
  * bytes that start on chunk boundaries.  Returns 1 when the fused kernels
  * can take the request, 0 when the caller must run the product and

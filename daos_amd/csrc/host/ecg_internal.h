@@ -90,6 +90,10 @@ struct ecg_ctx {
 	 * and uploaded on first use under `lock`, kept until ecg_ctx_destroy
 	 * (ecg_repair.c) */
 	void *repair_tbl[ECG_KMAX_K][ECG_KMAX_R];
+	/* device set tables of ecg_recover_masks by (k, p): one entry per erasure
+	 * set (ecg_kabi.h ECG_RM_ENT_Q), handled as repair_tbl is
+	 * (ecg_recover_masks.c) */
+	void *rm_tbl[ECG_RM_MAX_K][ECG_RM_MAX_P];
 	ecg_stats_t stats;		/* telemetry (ecg_get_stats), updated with atomics */
 };
 
@@ -146,6 +150,12 @@ int ecg_segs_launch(const struct ecg_segs *v, const void *segs_dev, hipStream_t 
 
 /* repair row tables (ecg_repair.c) */
 void ecg_repair_ctx_fini(ecg_ctx_t *ctx);
+/* Does [a, a + alen) meet the cells base + i*si + j*sj, i < ni, j < nj, each
+ * len bytes long? (ecg_repair.c) */
+int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
+		      int64_t sj, uint64_t len);
+/* erasure set tables (ecg_recover_masks.c) */
+void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx);
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);

@@ -1,0 +1,223 @@
+/*
+ * ecg_recover_masks.c -- recovery with one erasure set per stripe
+ * (include/ecg.h ecg_recover_masks, ecg_erasure_sets, ecg_erasure_set_index).
+ *
+ * What it replaces: ecg_recover takes one err_list for a whole batch, so a
+ * rebuild batch whose stripes lost different shards, or a scrub whose
+ * checksums name different cells per stripe, is sorted by erasure set on the
+ * host and issued as one launch per set.  Here the sets are mask words that
+ * stay on the device (ecg_csum_mask writes them from checksums): one launch
+ * reads them, and each block picks its rows, survivors and destinations per
+ * stripe (kernels/ecg_recover_masks_kernels.hip).
+ *
+ * The set table: every nonempty set of at most p of the k + p cells has an
+ * index (ecg_kabi.h ecg_erasure_set_read); entry i holds what ecg_recov_rows
+ * gives for the set of index i listed in ascending cell order -- e, out_idx,
+ * dec_idx and the e x k rows as perm tables, laid out as the kernels stage
+ * them (ECG_RM_ENT_Q).  Built once per (k, p) and context and kept until the
+ * context goes: 3 entries for EC_2P1, 1159 entries of 1056 bytes (1.2 MB)
+ * for k = 16, p = 3, the largest.
+ */
+#include <stdlib.h>
+#include <string.h>
+
+#include "ecg_internal.h"
+
+static int check_kp(const char *fn, int k, int p)
+{
+	if (k < 1 || k > ECG_RM_MAX_K || p < 1 || p > ECG_RM_MAX_P)
+		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
+				ECG_RM_MAX_K, ECG_RM_MAX_P);
+	return 0;
+}
+
+int ecg_erasure_sets(int k, int p)
+{
+	int rc = check_kp("erasure_sets", k, p);
+
+	return rc ? rc : (int)ecg_erasure_set_count(k, p);
+}
+
+int ecg_erasure_set_index(int k, int p, uint32_t mask)
+{
+	int rc = check_kp("erasure_set_index", k, p);
+
+	if (rc)
+		return rc;
+	rc = ecg_erasure_set_read(mask, k, p);
+	if (rc == ECG_RM_RANGE)
+		return ecg_fail(-ECG_DER_INVAL, "erasure_set_index: mask 0x%x names a cell at or above k+p=%d", mask,
+				k + p);
+	if (rc == ECG_RM_LOSS)
+		return ecg_fail(-ECG_DER_DATA_LOSS, "erasure_set_index: mask 0x%x has more than p=%d cells", mask, p);
+	return rc;	/* the index, or -1 for the empty set */
+}
+
+/* Host image of the (k, p) set table: every mask of at most p bits below
+ * k + p fills the entry of its index. */
+static int build_sets(int k, int p, uint32_t *img, uint32_t nsets)
+{
+	unsigned char en[(ECG_RM_MAX_K + ECG_RM_MAX_P) * ECG_RM_MAX_K];
+	const uint32_t entw = 4u * ECG_RM_ENT_Q(k, p), per_j = (uint32_t)p + 1u;
+	const int n = k + p;
+	uint32_t seen = 0;
+
+	ecg_gf_init();
+	ecg_gen_cauchy1(k, p, en);
+	for (uint32_t mask = 1; mask < (1u << n); mask++) {	/* n <= 19 */
+		unsigned char rows[ECG_MAX_P * ECG_MAX_K];
+		uint32_t err[ECG_RM_MAX_P], out_idx[ECG_MAX_P], dec_idx[ECG_MAX_K], *ent;
+		int e = 0, reused, idx, rc;
+
+		if (__builtin_popcount(mask) > p)
+			continue;
+		for (uint32_t m = mask; m; m &= m - 1u)	/* ascending cell order */
+			err[e++] = (uint32_t)__builtin_ctz(m);
+		idx = ecg_erasure_set_read(mask, k, p);
+		if (idx < 0 || (uint32_t)idx >= nsets)
+			return ecg_fail(-ECG_DER_INVAL, "recover_masks: set 0x%x has no index", mask);
+		rc = ecg_recov_rows(k, p, en, err, e, rows, out_idx, dec_idx, &reused);
+		if (rc)
+			return rc;
+		ent = img + (size_t)idx * entw;
+		ent[0] = (uint32_t)e;
+		for (int r = 0; r < e; r++)
+			ent[1 + r] = out_idx[r];
+		for (int j = 0; j < k; j++) {
+			uint32_t *tj = ent + 8 + 4u * per_j * (uint32_t)j;
+
+			((unsigned char *)(ent + 4))[j] = (unsigned char)dec_idx[j];
+			for (int r = 0; r < e; r++) {
+				ecg_ptbl_t t;
+
+				ecg_build_ptbl(rows[r * k + j], &t);
+				tj[4 * r + 0] = t.t0lo;
+				tj[4 * r + 1] = t.t0hi;
+				tj[4 * r + 2] = t.t1lo;
+				tj[4 * r + 3] = t.t1hi;
+				tj[4 * p + r] = t.t2;
+			}
+		}
+		seen++;
+	}
+	if (seen != nsets)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: %u sets built, %u expected", seen, nsets);
+	return 0;
+}
+
+/* Device copy of the (k, p) set table, built once per (k, p) and context
+ * (ctx->lock); synchronous on first use. */
+static int set_table(ecg_ctx_t *ctx, int k, int p, const void **out)
+{
+	int rc = 0;
+
+	pthread_mutex_lock(&ctx->lock);
+	if (ctx->rm_tbl[k - 1][p - 1] == NULL) {
+		const uint32_t nsets = ecg_erasure_set_count(k, p);
+		const size_t bytes = (size_t)nsets * 16u * ECG_RM_ENT_Q(k, p);
+		uint32_t *img = calloc(1, bytes);
+		void *dev = NULL;
+		hipError_t e;
+
+		if (img == NULL) {
+			rc = ecg_fail(-ECG_DER_NOMEM, "recover_masks set table");
+		} else {
+			rc = build_sets(k, p, img, nsets);
+			if (rc == 0) {
+				e = hipMalloc(&dev, bytes);
+				if (e == hipSuccess)
+					e = hipMemcpy(dev, img, bytes, hipMemcpyHostToDevice);
+				if (e != hipSuccess) {
+					if (dev)
+						(void)hipFree(dev);
+					rc = ecg_hip_fail(e, "recover_masks set table");
+				} else {
+					ctx->rm_tbl[k - 1][p - 1] = dev;
+				}
+			}
+			free(img);
+		}
+	}
+	*out = ctx->rm_tbl[k - 1][p - 1];
+	pthread_mutex_unlock(&ctx->lock);
+	return rc;
+}
+
+void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx)
+{
+	for (int k = 0; k < ECG_RM_MAX_K; k++)
+		for (int p = 0; p < ECG_RM_MAX_P; p++)
+			if (ctx->rm_tbl[k][p]) {
+				(void)hipFree(ctx->rm_tbl[k][p]);
+				ctx->rm_tbl[k][p] = NULL;
+			}
+}
+
+int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
+		      void *stripes, int64_t stripe_stride,
+		      const uint32_t *masks, void *result, unsigned flags, void *stream)
+{
+	const void *settbl = NULL;
+	ecg_mm_params_t *prm;
+	hipStream_t st;
+	hipError_t he;
+	uint32_t kid = 0;
+	int rc, e, bytewise;
+
+	rc = check_kp("recover_masks", k, p);
+	if (rc)
+		return rc;
+	if (flags & ~ECG_RM_SPARSE)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: unknown flags 0x%x", flags);
+	if (result == NULL || (uintptr_t)result % 8u)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: result must be 8-byte aligned device memory");
+	if (S && (masks == NULL || (uintptr_t)masks % 4u))
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: masks must be 4-byte aligned device memory");
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: NULL context");
+	if (S && C && stripes == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: NULL stripes");
+	/* the kernel reads mask words while other blocks write cells */
+	if (S && C && ecg_cells_overlap(masks, 4ull * S, stripes, S, stripe_stride, k + p, (int64_t)C, C))
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks: masks overlaps the stripes");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+
+	/* result = {0, UINT64_MAX, 0, 0}: nothing recovered, nothing left */
+	he = hipMemsetAsync(result, 0, 32, st);
+	if (he == hipSuccess)
+		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
+	if (he != hipSuccess)
+		return ecg_hip_fail(he, "recover_masks memset");
+	if (S == 0 || C == 0)
+		return 0;
+
+	rc = set_table(ctx, k, p, &settbl);
+	if (rc)
+		return rc;
+	prm = calloc(1, sizeof(*prm));
+	if (prm == NULL)
+		return ecg_fail(-ECG_DER_NOMEM, "recover_masks: calloc");
+	prm->src = stripes;
+	prm->dst = stripes;
+	prm->src_stripe_stride = stripe_stride;
+	prm->dst_stripe_stride = stripe_stride;
+	prm->cell_bytes = C;
+	prm->nstripes = S;
+	prm->k = (uint32_t)k;
+	prm->rows = (uint32_t)p;
+	bytewise = ctx->cfg.variant == 2 || ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u;
+
+	ecg_trace_push("ecg:recover_masks");
+	e = ecg_k_launch_recover_masks(prm, settbl, masks, (uint64_t *)result, bytewise,
+				       (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
+	ecg_trace_pop();
+	free(prm);
+	if (e != 0)
+		return ecg_hip_fail((hipError_t)e, "recover_masks kernel launch");
+	ECG_STAT_ADD(ctx, launches, 1);
+	ecg_set_last_kernel(ecg_k_recover_masks_kernel_name(kid));
+	return 0;
+}

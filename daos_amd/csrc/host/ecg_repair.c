@@ -111,8 +111,8 @@ void ecg_repair_ctx_fini(ecg_ctx_t *ctx)
 
 /* Does [a, a + alen) meet the cells base + i*si + j*sj, i < ni, j < nj, each
  * len bytes long?  (Their bounding range: strides may be negative.) */
-static int overlaps(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
-		    int64_t sj, uint64_t len)
+int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
+			int64_t sj, uint64_t len)
 {
 	const int64_t ei = (ni - 1) * si, ej = (nj - 1) * sj;
 	const int64_t lo = (ei < 0 ? ei : 0) + (ej < 0 ? ej : 0);
@@ -148,8 +148,8 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		return ecg_fail(-ECG_DER_INVAL, "repair: NULL cells");
 	/* the kernel reads status words while other blocks write cells */
 	if (S && C &&
-	    (overlaps(status, 4ull * S, data, S, data_stripe_stride, k, (int64_t)C, C) ||
-	     overlaps(status, 4ull * S, parity, S, parity_stripe_stride, p, parity_cell_stride, C)))
+	    (ecg_cells_overlap(status, 4ull * S, data, S, data_stripe_stride, k, (int64_t)C, C) ||
+	     ecg_cells_overlap(status, 4ull * S, parity, S, parity_stripe_stride, p, parity_cell_stride, C)))
 		return ecg_fail(-ECG_DER_INVAL, "repair: status overlaps the data or parity cells");
 	rc = ecg_ctx_enter(ctx);
 	if (rc)

@@ -640,7 +640,55 @@ ecg_csum_compare_kernel(const uint8_t *got, const uint8_t *want, uint64_t n, uns
 }
 constexpr uint32_t KID_COMPARE = ECG_KID_CSUM + N_CSUM + N_SPLIT + N_GROUP;
 
+// Which cells' checksums differ, per stripe (ecg_csum_mask): a thread takes
+// one (stripe, cell) and compares its nch checksums of LEN bytes; a cell with
+// a mismatch sets its bit in the stripe's mask word.  Byte loads, as above.
+template <int LEN>
+__global__ void __launch_bounds__(CS_BLOCK)
+ecg_csum_mask_kernel(const uint8_t *got, const uint8_t *want, uint32_t nstripes, uint32_t ncells, uint32_t nch,
+		     uint64_t stripe_stride, uint64_t cell_stride, uint32_t first_cell, uint32_t *masks)
+{
+	const uint64_t n = (uint64_t)nstripes * ncells;
+
+	for (uint64_t t = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; t < n; t += (uint64_t)gridDim.x * blockDim.x) {
+		const uint32_t s = (uint32_t)(t / ncells), i = (uint32_t)(t % ncells);
+		const uint64_t at = ((uint64_t)s * stripe_stride + (uint64_t)i * cell_stride) * LEN;
+		uint32_t d = 0;
+
+		for (uint64_t b = 0; b < (uint64_t)nch * LEN; b++)
+			d |= (uint32_t)(got[at + b] ^ want[at + b]);
+		if (d)
+			atomicOr(&masks[s], 1u << (first_cell + i));
+	}
+}
+constexpr uint32_t KID_MASK = KID_COMPARE + 1;
+
 } // namespace
+
+extern "C" int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
+				      uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride,
+				      uint32_t first_cell, uint32_t len, uint32_t *masks, void *stream,
+				      uint32_t *kernel_id)
+{
+	const uint64_t n = (uint64_t)nstripes * ncells;
+	uint64_t nb = (n + CS_BLOCK - 1) / CS_BLOCK;
+
+	if (n == 0 || nch == 0)
+		return (int)hipSuccess;
+	if (nb > 256 * 4)
+		nb = 256 * 4;
+	void (*fn)(const uint8_t *, const uint8_t *, uint32_t, uint32_t, uint32_t, uint64_t, uint64_t, uint32_t,
+		   uint32_t *) =
+		len == 2 ? ecg_csum_mask_kernel<2> : len == 4 ? ecg_csum_mask_kernel<4>
+		: len == 8 ? ecg_csum_mask_kernel<8> : nullptr;
+	if (fn == nullptr || masks == nullptr || first_cell + (uint64_t)ncells > 32)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL(fn, dim3((uint32_t)nb), dim3(CS_BLOCK), 0, (hipStream_t)stream, (const uint8_t *)got,
+			   (const uint8_t *)want, nstripes, ncells, nch, stripe_stride, cell_stride, first_cell, masks);
+	if (kernel_id)
+		*kernel_id = KID_MASK;
+	return (int)hipGetLastError();
+}
 
 extern "C" int ecg_k_launch_csum_compare(const void *got, const void *want, uint64_t n, uint32_t len,
 					 uint64_t *result, void *stream, uint32_t *kernel_id)
@@ -667,6 +715,8 @@ extern "C" const char *ecg_k_csum_kernel_name(uint32_t id)
 {
 	if (id == KID_COMPARE)
 		return "ecg_csum_compare_kernel";
+	if (id == KID_MASK)
+		return "ecg_csum_mask_kernel";
 	if (id >= ECG_KID_CSUM && id < ECG_KID_CSUM + N_CSUM)
 		return g_csum[id - ECG_KID_CSUM].name;
 	if (id >= ECG_KID_CSUM + N_CSUM && id < ECG_KID_CSUM + N_CSUM + N_SPLIT)

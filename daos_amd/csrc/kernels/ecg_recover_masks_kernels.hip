@@ -1,0 +1,283 @@
+// ecg_recover_masks_kernels.hip -- recovery with one erasure set per stripe
+// (ecg_recover_masks): a rebuild batch whose stripes lost different shards, or
+// the second half of a checksum-driven scrub, in one launch.
+//
+// A block row takes `grp` consecutive stripes (1 .. 64): lane l of every wave
+// reads the mask word of the row's stripe l (one coalesced load), reads it
+// with the one reading the host shares (ecg_kabi.h ecg_erasure_set_read), and
+// a ballot leaves the stripes with a valid set as a wave-uniform 64-bit mask.
+// The block walks the set bits.  For a stripe whose mask reads as set i it
+// takes entry i of the (k, p) set table the host keeps on the device (host/
+// ecg_recover_masks.c): e, the erased cells in ecg_recov_rows's output order,
+// the k survivors, and the e x k perm tables already in the product's LDS
+// layout -- staged with one 16-byte copy per thread, and not at all when the
+// previous stripe of the block had the same set.  k source addresses and e
+// destination addresses follow from the entry (wave-uniform), and the columns
+// run the product's column code (ecg_mm_dev.h mm_ptr_item) with rows = e.
+//
+// Every address derives from the table entry of a validated index, never
+// from raw mask bits, so all 2^32 mask values are safe; destinations are
+// erased cells and sources survivors, so the in-place write has no hazard.
+//
+// One kernel, two grids (the launcher's choice, ECG_RM_SPARSE): grp = 1 with
+// a block per column when every stripe has work, grp = 64 with a few column
+// blocks striding when almost none has -- a clean batch then costs S / 64 *
+// grid.x blocks of one load each.  Column-block 0 of a row counts its stripes
+// into `result`, one lane per stripe.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../ecg_kabi.h"
+#include "ecg_mm_dev.h"
+
+namespace {
+
+// The row's mask words: *il = this lane's reading of stripe row * grp + lane
+// (ECG_RM_NONE past the row or the batch), returned the mask of the stripes
+// to recover -- the same in every wave of the block, the words being
+// read-only for the launch.  nsets bounds the index once more (it cannot fail:
+// the reading is a bijection onto 0 .. nsets-1).
+__device__ __forceinline__ uint64_t rm_scan(const uint32_t *__restrict__ masks, uint32_t nstripes, uint32_t row,
+					    uint32_t grp, int k, int p, uint32_t nsets,
+					    const u32x4 *__restrict__ settbl, uint32_t entq,
+					    unsigned long long *result, int *il)
+{
+	const uint32_t l = threadIdx.x & 63u;
+	const uint64_t s = (uint64_t)row * grp + l;
+	int idx = ECG_RM_NONE;
+
+	if (l < grp && s < nstripes)
+		idx = ecg_erasure_set_read(masks[s], k, p);
+	if (idx >= (int)nsets)
+		idx = ECG_RM_RANGE;
+	if (blockIdx.x == 0 && threadIdx.x < 64 && idx != ECG_RM_NONE) {
+		if (idx >= 0) {
+			atomicAdd(&result[0], 1ull);
+			atomicAdd(&result[2], (unsigned long long)settbl[(uint64_t)idx * entq][0]);
+		} else {
+			atomicMin(&result[1], (unsigned long long)s);
+			atomicAdd(&result[3], 1ull);
+		}
+	}
+	*il = idx;
+	return __ballot(idx >= 0);
+}
+
+// byte j of the entry's survivor word
+__device__ __forceinline__ uint32_t rm_dec(const u32x4 &d, int j)
+{
+	return (d[j / 4] >> (8 * (j % 4))) & 0xffu;
+}
+
+} // namespace
+
+// K as ecg_mm_kernel's (0 = runtime-shaped), RM = p output rows at most (a
+// stripe's e <= p rows run with rows = e).  16-byte lanes only: the stripes
+// and their stride 16-byte aligned, C % 16 == 0 (the launcher sends everything
+// else to the byte kernel), so a partial last column is a lane mask.
+template <int K, int RM>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, RM, 16) ? ECG_MM_WPE(K, RM, 16) : 1)
+ecg_recover_masks_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ settbl,
+			 const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp,
+			 uint32_t nsets)
+{
+	constexpr int KM = K ? K : ECG_KMAX_K;
+	constexpr int PER_J = RM + 1;	// RM + T2V, RM <= 4
+	__shared__ u32x4 s_tbl[KM * PER_J];
+	const int k = K ? K : (int)P.k;
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const uint32_t lo = lane_off<16>();
+	const uint32_t entq = ECG_RM_ENT_Q(k, RM);
+	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+	int staged = -1;	// the set whose tables s_tbl holds
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		int il;
+		uint64_t todo = rm_scan(masks, P.nstripes, row, grp, k, RM, nsets, settbl, entq, result, &il);
+
+		while (todo) {
+			const int l = __ffsll((unsigned long long)todo) - 1;
+			const int idx = __builtin_amdgcn_readlane(il, l);
+			const uint32_t s = row * grp + (uint32_t)l;
+			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
+
+			todo &= todo - 1;
+			if (staged != idx) {
+				__syncthreads();	// the previous stripe's columns are done with s_tbl
+				if ((int)threadIdx.x < k * PER_J)
+					s_tbl[threadIdx.x] = ent[2 + threadIdx.x];
+				__syncthreads();
+				staged = idx;
+			}
+
+			// the set's rows, erased cells and survivors (wave-uniform)
+			const u32x4 hd = ent[0], dec = ent[1];
+			const int e = (int)hd[0];
+			const uint64_t sb = (uint64_t)(uintptr_t)P.src + (uint64_t)((int64_t)s * P.src_stripe_stride);
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+				const uint64_t cb = sb + cbase;
+				uint64_t a[KM + RM];
+				uint32_t z = 0;
+
+#pragma unroll
+				for (int j = 0; j < KM; j++) {
+					if (j < k) {
+						a[j] = cb + (uint64_t)rm_dec(dec, j) * C;
+						asm volatile("" : "+s"(a[j]));
+					}
+				}
+#pragma unroll
+				for (int r = 0; r < RM; r++) {
+					if (r < e) {
+						a[KM + r] = cb + (uint64_t)hd[1 + r] * C;
+						asm volatile("" : "+s"(a[KM + r]));
+					}
+				}
+				asm volatile("" : "+v"(z));
+				const u32x4 *tb = s_tbl + z;
+				// a partial last column is a lane mask (C % 16 == 0 here)
+				if (cbase + CHUNK_BYTES <= C || cbase + lo + 16 <= C)
+					mm_ptr_item<KM, RM, 16>(P, tb, k, e, s, cbase, lo, a);
+			}
+		}
+	}
+}
+
+// Any alignment, any length, any k <= 16 and p <= 3: a block takes 4 KiB
+// columns of one stripe at a time, a lane the bytes t, t + 256, ... of a
+// column.  Same scan, entries and counters as the lane kernel; the set's
+// tables are read where they lie (wave-uniform loads).
+__global__ void __launch_bounds__(BLOCK)
+ecg_recover_masks_byte_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ settbl,
+			      const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp,
+			      uint32_t nsets)
+{
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const int k = (int)P.k, p = (int)P.rows;
+	const int per_j = p + 1;
+	const uint32_t entq = ECG_RM_ENT_Q(k, p);
+	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		int il;
+		uint64_t todo = rm_scan(masks, P.nstripes, row, grp, k, p, nsets, settbl, entq, result, &il);
+
+		while (todo) {
+			const int l = __ffsll((unsigned long long)todo) - 1;
+			const int idx = __builtin_amdgcn_readlane(il, l);
+			const uint32_t s = row * grp + (uint32_t)l;
+			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
+			const u32x4 hd = ent[0];
+			const uint8_t *__restrict__ dec = reinterpret_cast<const uint8_t *>(ent + 1);
+			const int e = (int)hd[0];
+			uint8_t *sb = P.dst + (int64_t)s * P.dst_stripe_stride;
+
+			todo &= todo - 1;
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+
+				for (uint64_t i = cbase + threadIdx.x; i < cbase + CHUNK_BYTES && i < C; i += BLOCK) {
+					uint32_t o[ECG_RM_MAX_P] = {0u, 0u, 0u};
+
+					for (int j = 0; j < k; j++) {
+						const uint32_t x = sb[(uint64_t)dec[j] * C + i];
+						const u32x4 t2 = ent[2 + j * per_j + p];
+
+#pragma unroll
+						for (int r = 0; r < ECG_RM_MAX_P; r++) {
+							if (r < e) {
+								const u32x4 t = ent[2 + j * per_j + r];
+								const ecg_ptbl_t pt = {t[0], t[1], t[2], t[3], t2[r]};
+
+								o[r] ^= gf_mul1(pt, x);
+							}
+						}
+					}
+#pragma unroll
+					for (int r = 0; r < ECG_RM_MAX_P; r++)
+						if (r < e)
+							sb[(uint64_t)hd[1 + r] * C + i] = (uint8_t)o[r];
+				}
+			}
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
+// Dispatch
+// ---------------------------------------------------------------------------
+typedef void (*rm_fn_t)(const ecg_mm_params_t, const u32x4 *, const uint32_t *, unsigned long long *, uint32_t,
+			uint32_t);
+
+struct rmentry {
+	int k, rm;
+	rm_fn_t fn;
+	const char *name;
+};
+
+#define RME(K_, R_) {K_, R_, ecg_recover_masks_kernel<K_, R_>, "ecg_recover_masks_kernel<" #K_ ", " #R_ ">"}
+#define RMK(K_) RME(K_, 1), RME(K_, 2), RME(K_, 3)
+
+// the k of the DAOS EC classes; the rest runtime-shaped
+static const rmentry g_rm[] = {RMK(2), RMK(4), RMK(8), RMK(16), RMK(0)};
+#define N_RM ((uint32_t)(sizeof(g_rm) / sizeof(g_rm[0])))
+#define KID_RM_BYTE (ECG_KID_RECOVER_MASKS + N_RM)
+
+extern "C" const char *ecg_k_recover_masks_kernel_name(uint32_t id)
+{
+	if (id >= ECG_KID_RECOVER_MASKS && id < ECG_KID_RECOVER_MASKS + N_RM)
+		return g_rm[id - ECG_KID_RECOVER_MASKS].name;
+	if (id == KID_RM_BYTE)
+		return "ecg_recover_masks_byte_kernel";
+	return "?";
+}
+
+extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint32_t *masks,
+					  uint64_t *result, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
+					  void *stream, uint32_t *kernel_id)
+{
+	hipStream_t st = (hipStream_t)stream;
+	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+
+	if (p->nstripes == 0 || p->cell_bytes == 0)
+		return (int)hipSuccess;
+	if (p->k == 0 || p->k > ECG_RM_MAX_K || p->rows == 0 || p->rows > ECG_RM_MAX_P || settbl == nullptr ||
+	    masks == nullptr || result == nullptr || p->src != p->dst || p->src_stripe_stride != p->dst_stripe_stride)
+		return (int)hipErrorInvalidValue;
+	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
+	const uint32_t gxmax = sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X;
+	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < gxmax ? nchunk : gxmax);
+	const uint32_t nrow = p->nstripes / grp + (p->nstripes % grp != 0);
+	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (nrow < 65535 ? nrow : 65535);
+	const uint32_t nsets = ecg_erasure_set_count((int)p->k, (int)p->rows);
+
+	if (bytewise) {
+		hipLaunchKernelGGL(ecg_recover_masks_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p,
+				   (const u32x4 *)settbl, masks, (unsigned long long *)result, grp, nsets);
+		if (kernel_id)
+			*kernel_id = KID_RM_BYTE;
+		return (int)hipGetLastError();
+	}
+	// the lane kernel reads and writes dwordx4 at the cells' own addresses
+	if ((((uint64_t)(uintptr_t)p->src | (uint64_t)p->src_stripe_stride | p->cell_bytes) & 15u) != 0)
+		return (int)hipErrorInvalidValue;
+
+	uint32_t id = N_RM;
+	for (uint32_t i = 0; i < N_RM; i++)
+		if (g_rm[i].rm == (int)p->rows && (g_rm[i].k == (int)p->k || g_rm[i].k == 0)) {
+			id = i;
+			break;
+		}
+	if (id == N_RM)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL(g_rm[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, (const u32x4 *)settbl, masks,
+			   (unsigned long long *)result, grp, nsets);
+	if (kernel_id)
+		*kernel_id = ECG_KID_RECOVER_MASKS + id;
+	return (int)hipGetLastError();
+}

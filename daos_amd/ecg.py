@@ -64,6 +64,10 @@ _SIGS = [
     ("ecg_repair", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_repair_row", C.c_int, [C.c_int, C.c_int, C.c_int, u8p, u32p]),
+    ("ecg_recover_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, vp, C.c_uint,
+                                    vp]),
+    ("ecg_erasure_sets", C.c_int, [C.c_int, C.c_int]),
+    ("ecg_erasure_set_index", C.c_int, [C.c_int, C.c_int, C.c_uint32]),
     ("ecg_matmul_ptrs", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp), vp]),
     ("ecg_update_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), u8p, vp]),
     ("ecg_matmul_host", C.c_int, [vp, C.c_int, C.c_int, C.c_int, u8p, C.POINTER(u8p), C.POINTER(u8p), C.c_uint]),
@@ -195,6 +199,8 @@ _SIGS = [
     ("ecg_recover_csum_all", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, u32p, C.c_int,
                                        C.c_int, C.c_uint64, C.c_uint64, vp, vp, u32p, vp]),
     ("ecg_csum_compare", C.c_int, [vp, C.c_int, vp, vp, C.c_uint64, vp, vp]),
+    ("ecg_csum_mask", C.c_int, [vp, C.c_int, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
+                                C.c_uint32, vp, vp]),
     ("ecg_set_csum_all_route", C.c_int, [vp, C.c_uint32]),
 ]
 
@@ -408,6 +414,26 @@ def repair_row(k: int, p: int, cell: int):
     return coef[:k], np.array(list(idx)[:k], dtype=np.uint32)
 
 
+RM_SPARSE = 0x1     # ECG_RM_SPARSE
+
+
+def erasure_sets(k: int, p: int) -> int:
+    """ecg_erasure_sets: the number of erasure sets of at most p of the k + p cells."""
+    n = lib().ecg_erasure_sets(k, p)
+    if n < 0:
+        raise EcgError(n, "erasure_sets")
+    return n
+
+
+def erasure_set_index(k: int, p: int, mask: int) -> int:
+    """ecg_erasure_set_index: 0..erasure_sets(k, p)-1 for a mask of 1..p cells below k + p, -1
+    for mask 0; raises EcgError (DER_DATA_LOSS: more than p cells, DER_INVAL: out of range)."""
+    i = lib().ecg_erasure_set_index(k, p, int(mask))
+    if i < -1:
+        raise EcgError(i, "erasure_set_index")
+    return i
+
+
 # ---------------------------------------------------------------- device side
 class DeviceBuffer:
     def __init__(self, ctx: "Context", nbytes: int):
@@ -606,6 +632,15 @@ class Context:
         _chk(lib().ecg_repair(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
                               parity_cell_stride, parity_stripe_stride, status, result, stream), "repair")
 
+    def recover_masks(self, k: int, p: int, cell_bytes: int, nstripes: int, stripes: int, stripe_stride: int,
+                      masks: int, result: int, flags: int = 0, stream=None):
+        """ecg_recover_masks: recover() with one erasure set per stripe -- bit c of the device
+        word masks[s] = cell c of stripe s is erased; result: device memory for four uint64
+        (stripes recovered, lowest stripe left unrecoverable, cells regenerated, stripes left
+        unrecoverable).  flags: RM_SPARSE (few stripes have work; tuning only)."""
+        _chk(lib().ecg_recover_masks(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride, masks, result,
+                                     flags, stream), "recover_masks")
+
     def csum_extents(self, htype: int, chunksize: int, rec_size: int, rx_idx: int, rx_nr: int, buf: int,
                      ext_stride: int, n_ext: int, csums: int, stream=None):
         """Device checksums of n_ext extents (include/ecg_csum.h): csums[n_ext][nchunks]."""
@@ -646,6 +681,14 @@ class Context:
     def csum_compare(self, htype: int, got: int, want: int, n: int, result: int, stream=None):
         """Compare n device checksums; result: device memory for two uint64 (mismatches, lowest index)."""
         _chk(lib().ecg_csum_compare(self.h, htype, got, want, n, result, stream), "csum_compare")
+
+    def csum_mask(self, htype: int, got: int, want: int, nstripes: int, ncells: int, nch: int, stripe_stride: int,
+                  cell_stride: int, first_cell: int, masks: int, stream=None):
+        """ecg_csum_mask: masks[s] |= 1 << (first_cell + i) when any of the nch device checksums at
+        index s*stripe_stride + i*cell_stride + c differs between got and want (strides in
+        checksums); the masks recover_masks() reads."""
+        _chk(lib().ecg_csum_mask(self.h, htype, got, want, nstripes, ncells, nch, stripe_stride, cell_stride,
+                                 first_cell, masks, stream), "csum_mask")
 
     def set_csum_all_route(self, route: int = 0):
         """Source checksums of *_csum_all: 0 measured default, 1 fused kernel, 2 two passes."""

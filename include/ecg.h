@@ -252,6 +252,57 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
  * -ECG_DER_INVAL outside 0..k+p-1 or k/p out of range (k <= 16, p <= 8). */
 int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_idx);
 
+/* Recovery with one erasure set PER STRIPE, in one launch: a rebuild or
+ * degraded-read batch whose stripes lost different shards, and the second
+ * half of a checksum-driven scrub (ecg_csum.h: ecg_csum_extents ->
+ * ecg_memset(masks, 0) -> ecg_csum_mask -> ecg_recover_masks, four
+ * asynchronous calls on one stream; the masks never leave the device).
+ * Operands as ecg_recover's: [S][k+p][C] in logical cell order, stripe s at
+ * stripes + s*stripe_stride.  masks: device memory, nstripes words, 4-byte
+ * aligned, read only, not overlapping the stripes (-ECG_DER_INVAL); bit c of
+ * masks[s] = logical cell c of stripe s is erased.  With m = masks[s]:
+ *   m == 0                      the stripe is not touched and not counted
+ *   a bit at or above k+p set,  the stripe is not touched; it is counted in
+ *   or more than p bits set     result[3] and result[1] -- the device-side form
+ *                               of -ECG_DER_DATA_LOSS, the host never sees m
+ *   otherwise                   byte for byte what ecg_recover(err_list = the
+ *                               set bits of m in ascending order, nerrs =
+ *                               popcount(m), nstripes = 1) writes for that
+ *                               stripe (its survivors, rows and output order,
+ *                               the all-parity shortcut included), nothing else
+ * All 2^32 mask values are safe.  result (device, 4 x uint64, 8-byte aligned)
+ * = {stripes recovered, lowest stripe left unrecoverable (UINT64_MAX if
+ * none), cells regenerated, stripes left unrecoverable}; nstripes == 0 or
+ * cell_bytes == 0 leaves {0, UINT64_MAX, 0, 0}.  UNRECOVERABLE STRIPES ARE
+ * REPORTED THROUGH result ONLY: the call itself returns 0.
+ * Limits: k <= 16 and p <= 3 (every DAOS EC class), -ECG_DER_INVAL beyond.  Any
+ * alignment and length (16-byte aligned stripes and stride with cell_bytes %
+ * 16 == 0 run the 16-byte lane kernel, everything else a byte-granular one).
+ * flags: ECG_RM_SPARSE is a tuning hint and never changes a result -- few
+ * stripes carry erasures (a scrub), so the launch uses the grid whose cost on
+ * clean stripes is one mask load per 64 of them; without it every stripe is
+ * expected to have work (a rebuild) and the grid is the product's.
+ * ecg_set_launch's grid_x / grid_y override either grid; variant 2 forces
+ * the byte kernel.  Asynchronous on `stream`.
+ * Telemetry: ecg_get_stats' recover_stripes / recover_bytes are NOT advanced
+ * (how many stripes had work is known on the device only: read result);
+ * `launches` counts the launch.
+ * The first call for a (k, p) on a context builds that shape's table of
+ * erasure sets and uploads it synchronously (1.2 MB for k = 16, p = 3, the
+ * largest; kept until ecg_ctx_destroy). */
+#define ECG_RM_SPARSE 0x1u
+int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		      void *stripes, int64_t stripe_stride,
+		      const uint32_t *masks, void *result, unsigned flags, void *stream);
+/* The erasure sets ecg_recover_masks knows for (k, p), host only: their
+ * number N = sum_{e=1..p} C(k+p, e), and the index 0..N-1 of the set `mask`
+ * names (by size, then combinatorial rank C(c1,1) + C(c2,2) + C(c3,3) of its
+ * cells c1 < c2 < c3; a bijection).  ecg_erasure_set_index: -1 for mask 0,
+ * -ECG_DER_DATA_LOSS for more than p bits, -ECG_DER_INVAL for a bit at or above
+ * k+p; both -ECG_DER_INVAL for k > 16 or p > 3. */
+int ecg_erasure_sets(int k, int p);
+int ecg_erasure_set_index(int k, int p, uint32_t mask);
+
 /* ---- host-resident pipeline (PCIe-inclusive) ---------------------------- */
 /* One stripe, ISA-L ec_encode_data calling convention: pointers src[k],
  * dst[rows] (any alignment), `len` bytes each;

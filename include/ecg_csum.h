@@ -117,6 +117,29 @@ int ecg_recover_csum_all(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint
 int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want, uint64_t n,
 		     void *result, void *stream);
 
+/* Which cells of which stripes have a wrong checksum: the erasure masks of
+ * ecg_recover_masks (ecg.h), written on the device.  got / want: checksums of
+ * ecg_csum_len(type) bytes (2, 4 or 8); masks: device memory, nstripes words,
+ * 4-byte aligned.
+ *   masks[s] |= 1u << (first_cell + i)   for s < nstripes, i < ncells
+ * when any of the nch checksums at index s*stripe_stride + i*cell_stride + c
+ * (c < nch; strides in checksums, not bytes) differs between got and want.  It
+ * ORs into masks: zero them first (ecg_memset), then
+ *   two calls cover the separate data and parity arrays of
+ *     ecg_encode_csum_all, [cell][S][nch]: cell_stride = S*nch, stripe_stride
+ *     = nch; (first_cell, ncells) = (0, k) and (k, p);
+ *   one call covers ecg_csum_extents over a recovery-layout image,
+ *     [S][k+p][nch]: stripe_stride = (k+p)*nch, cell_stride = nch.
+ * The scrub ecg_verify / ecg_repair cannot do (p = 1; two or three wrong cells
+ * per stripe): ecg_csum_extents -> ecg_memset(masks) -> ecg_csum_mask ->
+ * ecg_recover_masks on one stream, no host round trip.
+ * -ECG_DER_INVAL when first_cell + ncells > 32, the hash type has no such
+ * checksum, or masks is NULL or misaligned.  Asynchronous on `stream`. */
+int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
+		  uint32_t nstripes, uint32_t ncells, uint32_t nch,
+		  uint64_t stripe_stride, uint64_t cell_stride,
+		  uint32_t first_cell, uint32_t *masks, void *stream);
+
 /* Route of the source checksums of ecg_encode_csum_all / ecg_recover_csum_all:
  * 0 the measured default per (hash type, k, output rows), 1 the fused kernel
  * wherever it can take the request, 2 always two passes.  Same results. */

@@ -18,6 +18,10 @@ report`).  Needs no GPU.
       other kernel file from this tree and from the tree before, every
       kernel of which must show identical figures (mm_ptr_item moved into
       ecg_mm_dev.h; exit 1 on any difference)
+  python tools/fused_resources.py --recover-masks RM.txt [NEW.txt BASE.txt]...
+      the ecg_recover_masks kernels (remarks of
+      ecg_recover_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
+      exit 1 if one uses scratch.  NEW BASE pairs as for --repair
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -101,25 +105,29 @@ def verify_table(verify_txt, product_txt=None):
 
 
 REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
+RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
 ANY = re.compile(r"(\S+)()()")
 
 
-def repair_table(repair_txt, *pairs):
-    """Table of the ecg_repair kernels (remarks of ecg_repair_kernels.hip), exit 1 on scratch;
-    then every kernel of each (new, base) pair of remarks files compared field by field."""
-    rep = parse_named(repair_txt, REPAIR)
+def repair_table(repair_txt, *pairs, pattern=REPAIR, what="repair"):
+    """Table of the ecg_repair kernels (remarks of ecg_repair_kernels.hip), or with
+    pattern=RECOVER_MASKS of the ecg_recover_masks kernels, exit 1 on scratch; then every
+    kernel of each (new, base) pair of remarks files compared field by field."""
+    rep = parse_named(repair_txt, pattern)
     bad = 0
     print("| kernel | " + " | ".join(FIELDS) + " |")
     print("|" + "---|" * (1 + len(FIELDS)))
-    for key in sorted(rep, key=lambda t: (t[0] != "ecg_repair_kernel", t[1] == 0, t[1])):
-        name, k, _ = key
+    for key in sorted(rep, key=lambda t: ("byte" in t[0], t[1] == 0, t[1], t[2])):
+        name, k, r = key
         v = rep[key]
         label = f"`{name}<{k}>`" if k >= 0 else f"`{name}`"
+        if r >= 0:
+            label = f"`{name}<{k},{r}>`"
         print(f"| {label} | " + " | ".join(str(v.get(f, "")) for f in FIELDS) + " |")
         if v.get("ScratchSize [bytes/lane]") or v.get("VGPRs Spill"):
             print(f"SCRATCH in {label}", file=sys.stderr)
             bad = 1
-    print(f"\nrepair kernels: {len(rep)}, " + ("SCRATCH USED" if bad else "none uses scratch"))
+    print(f"\n{what} kernels: {len(rep)}, " + ("SCRATCH USED" if bad else "none uses scratch"))
     for new_txt, base_txt in zip(pairs[0::2], pairs[1::2]):
         new, base = parse_named(new_txt, ANY), parse_named(base_txt, ANY)
         diff = [key[0] for key in sorted(set(new) | set(base)) if new.get(key) != base.get(key)]
@@ -135,6 +143,8 @@ def main():
         return verify_table(*sys.argv[2:4])
     if sys.argv[1] == "--repair":
         return repair_table(*sys.argv[2:])
+    if sys.argv[1] == "--recover-masks":
+        return repair_table(*sys.argv[2:], pattern=RECOVER_MASKS, what="recover_masks")
     new = parse(sys.argv[1])
     base = parse(sys.argv[2]) if len(sys.argv) > 2 else None
     bad = 0
