@@ -386,6 +386,63 @@ static inline ECG_KABI_HD int ecg_erasure_set_read(uint32_t mask, int k, int p)
 	return (int)idx;
 }
 /*
+ * Which cells of a stripe ecg_csum_masked checksums (kernels/
+ * ecg_csum_kernels.hip), from the stripe's mask word: nothing unless
+ * ecg_erasure_set_read reads the word as a set; `which` bit 0 the cells the
+ * set names, bit 1 the k lowest cells it does not name -- the dec_idx of
+ * ecg_recov_rows for the set in ascending order (its all-parity shortcut
+ * reads cells 0 .. k-1, which are the k lowest then too).  Shared by the host
+ * and the kernels; *valid = the word reads as a set.
+ */
+static inline ECG_KABI_HD uint32_t ecg_csum_masked_sel(uint32_t mask, int k, int p, uint32_t which, int *valid)
+{
+	uint32_t surv, sel = 0;
+
+	*valid = ecg_erasure_set_read(mask, k, p) >= 0;
+	if (!*valid)
+		return 0;
+	/* k + p - e >= k cells survive: drop the highest p - e of them */
+	surv = ~mask & ((1u << (k + p)) - 1u);
+	for (int i = __builtin_popcount(surv); i > k; i--)
+		surv &= ~(0x80000000u >> __builtin_clz(surv));
+	if (which & 1u)
+		sel |= mask;
+	if (which & 2u)
+		sel |= surv;
+	return sel;
+}
+
+/*
+ * ecg_csum_masked: stripes [S][k+p][C] at src + s*stripe_stride; a wave takes
+ * one (stripe s, r-th selected cell, chunk c) of the S x slots x nch items
+ * (slots = the most cells `which` can select: p, k or k + p) and skips those
+ * with r >= popcount(sel(masks[s])).  Chunk c of a cell is [c*chunk_bytes,
+ * min((c+1)*chunk_bytes, C)); out[(s*(k+p) + cell)*nch + c] = its checksum.
+ * The item (s, 0, 0) counts its stripe into result (NULL: not counted):
+ * result[0] += stripes with a valid set, result[1] = min(result[1], lowest
+ * stripe whose non-zero mask is no set), result[2] += cells checksummed,
+ * result[3] += stripes whose non-zero mask is no set.
+ */
+typedef struct ecg_csum_masked_params {
+	const uint8_t *src;
+	uint8_t *out;
+	const void *tbl;
+	const uint32_t *masks;
+	uint64_t *result;
+	int64_t stripe_stride;
+	uint64_t cell_bytes;
+	uint64_t chunk_bytes;
+	uint64_t init, xorout, poly;
+	uint32_t nstripes;
+	uint32_t nch;
+	uint32_t k, p;
+	uint32_t which;
+	uint32_t slots;
+	uint32_t type;
+	uint32_t pad;
+} ecg_csum_masked_params_t;
+
+/*
  * The set table of one (k, p), device memory, built by host/
  * ecg_recover_masks.c: entry i (the set of index i) is ECG_RM_ENT_Q(k, p)
  * 16-byte words,
@@ -431,6 +488,9 @@ const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
 int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
 			   uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride, uint32_t first_cell,
 			   uint32_t len, uint32_t *masks, void *stream, uint32_t *kernel_id);
+/* ecg_csum_masked (kernels/ecg_csum_kernels.hip); max_blocks 0 = default. */
+int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
+			     uint32_t *kernel_id);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of

@@ -790,6 +790,179 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 	return 0;
 }
 
+/* [a, a + alen) and [b, b + blen) share a byte */
+static int ranges_overlap(const void *a, uint64_t alen, const void *b, uint64_t blen)
+{
+	return alen && blen && (uintptr_t)a < (uintptr_t)b + blen && (uintptr_t)b < (uintptr_t)a + alen;
+}
+
+/* The geometry of an ecg_csum_masked call once its arguments passed */
+struct masked_geom {
+	uint64_t rcs;		/* record chunk bytes */
+	uint64_t bytes;		/* of one [S][k+p][nch] checksum array */
+	uint32_t nch;
+};
+
+/* Argument checks of ecg_csum_masked for the array `csums` (`what` names it),
+ * everything but the context; result == NULL is accepted with need_result = 0. */
+static int masked_check(const char *fn, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
+			uint32_t S, const void *stripes, int64_t stripe_stride, const uint32_t *masks, unsigned which,
+			const void *csums, const char *what, const void *result, int need_result, unsigned flags,
+			struct masked_geom *g)
+{
+	const int cl = ecg_csum_len(type);
+	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
+	uint64_t nch, bytes;
+
+	memset(g, 0, sizeof(*g));
+	if (cl < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "%s: hash type %d not supported", fn, type);
+	if (k < 1 || k > ECG_RM_MAX_K || p < 1 || p > ECG_RM_MAX_P)
+		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
+				ECG_RM_MAX_K, ECG_RM_MAX_P);
+	if (which < 1 || which > (ECG_CM_ERASED | ECG_CM_SURVIVORS))
+		return ecg_fail(-ECG_DER_INVAL, "%s: which 0x%x is not ECG_CM_ERASED, ECG_CM_SURVIVORS or both", fn,
+				which);
+	if (flags & ~ECG_RM_SPARSE)
+		return ecg_fail(-ECG_DER_INVAL, "%s: unknown flags 0x%x", fn, flags);
+	if (rcs == 0)
+		return ecg_fail(-ECG_DER_INVAL, "%s: chunksize and rec_size must not be 0", fn);
+	if (C % rec_size)
+		return ecg_fail(-ECG_DER_INVAL, "%s: cell_bytes %llu is not a multiple of rec_size %llu", fn,
+				(unsigned long long)C, (unsigned long long)rec_size);
+	if (masks == NULL || (uintptr_t)masks % 4u)
+		return ecg_fail(-ECG_DER_INVAL, "%s: masks must be 4-byte aligned device memory", fn);
+	if ((need_result && result == NULL) || (uintptr_t)result % 8u)
+		return ecg_fail(-ECG_DER_INVAL, "%s: result must be 8-byte aligned device memory", fn);
+	nch = C / rcs + (C % rcs != 0);
+	if (nch > UINT32_MAX || __builtin_mul_overflow(nch * (uint64_t)(k + p), (uint64_t)cl * S, &bytes))
+		return ecg_fail(-ECG_DER_INVAL, "%s: too many checksums", fn);
+	if (S && C && (stripes == NULL || csums == NULL))
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL stripes or %s", fn, what);
+	if (S && C && ecg_cells_overlap(csums, bytes, stripes, S, stripe_stride, k + p, (int64_t)C, C))
+		return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps the stripes", fn, what);
+	if (C && ranges_overlap(csums, bytes, masks, 4ull * S))
+		return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps the masks", fn, what);
+	g->rcs = rcs;
+	g->bytes = bytes;
+	g->nch = (uint32_t)nch;
+	return 0;
+}
+
+/* One ecg_csum_masked launch on st; result NULL = nothing counted. */
+static int masked_launch(ecg_ctx_t *ctx, int type, const struct masked_geom *g, int k, int p, uint64_t C, uint32_t S,
+			 const void *stripes, int64_t stripe_stride, const uint32_t *masks, unsigned which,
+			 void *csums, void *result, hipStream_t st)
+{
+	ecg_csum_masked_params_t prm;
+	uint32_t kid = 0;
+	int rc, e;
+
+	memset(&prm, 0, sizeof(prm));
+	if (type != ECG_HASH_ADLER32) {
+		rc = crc_tables(ctx, type, &prm.tbl);
+		if (rc)
+			return rc;
+		prm.poly = g_defs[type].poly;
+		prm.init = g_defs[type].init;
+		prm.xorout = g_defs[type].xorout;
+	}
+	prm.src = stripes;
+	prm.out = csums;
+	prm.masks = masks;
+	prm.result = result;
+	prm.stripe_stride = stripe_stride;
+	prm.cell_bytes = C;
+	prm.chunk_bytes = g->rcs;
+	prm.nstripes = S;
+	prm.nch = g->nch;
+	prm.k = (uint32_t)k;
+	prm.p = (uint32_t)p;
+	prm.which = which;
+	prm.slots = (which & ECG_CM_ERASED ? (uint32_t)p : 0) + (which & ECG_CM_SURVIVORS ? (uint32_t)k : 0);
+	prm.type = (uint32_t)type;
+	ecg_trace_push("ecg:csum_masked");
+	e = ecg_k_launch_csum_masked(&prm, (void *)st, ctx->csum_blocks, &kid);
+	ecg_trace_pop();
+	if (e != 0)
+		return ecg_hip_fail((hipError_t)e, "csum_masked kernel launch");
+	ECG_STAT_ADD(ctx, launches, 1);
+	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	return 0;
+}
+
+/* ECG_RM_SPARSE is accepted and ignored: the one grid serves dense and clean
+ * batches alike (a clean stripe's items are one mask load each). */
+int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, int k, int p,
+		    uint64_t C, uint32_t S, const void *stripes, int64_t stripe_stride, const uint32_t *masks,
+		    unsigned which, void *csums, void *result, unsigned flags, void *stream)
+{
+	struct masked_geom g;
+	hipStream_t st;
+	hipError_t he;
+	int rc;
+
+	rc = masked_check("csum_masked", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride, masks, which,
+			  csums, "csums", result, 1, flags, &g);
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_masked: NULL context");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	/* result = {0, UINT64_MAX, 0, 0}, as ecg_recover_masks presets it */
+	he = hipMemsetAsync(result, 0, 32, st);
+	if (he == hipSuccess)
+		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
+	if (he != hipSuccess)
+		return ecg_hip_fail(he, "csum_masked memset");
+	if (S == 0 || C == 0)
+		return 0;
+	return masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks, which, csums, result, st);
+}
+
+int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *stripes,
+			   int64_t stripe_stride, const uint32_t *masks, void *result, unsigned flags, int type,
+			   uint64_t chunksize, uint64_t rec_size, void *csums, void *src_csums, void *stream)
+{
+	const int one = src_csums != NULL && src_csums == csums;	/* one array, one which = 3 launch */
+	struct masked_geom g;
+	hipStream_t st;
+	int rc;
+
+	/* both halves' argument errors before anything is queued */
+	rc = ecg_recover_masks_check("recover_masks_csum", 1, k, p, C, S, stripes, stripe_stride, masks, result, flags);
+	if (rc)
+		return rc;
+	rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride, masks,
+			  one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, "csums", NULL, 0, flags, &g);
+	if (rc)
+		return rc;
+	if (src_csums != NULL && !one) {
+		rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride,
+				  masks, ECG_CM_SURVIVORS, src_csums, "src_csums", NULL, 0, flags, &g);
+		if (rc)
+			return rc;
+		if (S && C && ranges_overlap(csums, g.bytes, src_csums, g.bytes))
+			return ecg_fail(-ECG_DER_INVAL,
+					"recover_masks_csum: src_csums must be csums itself or not overlap it");
+	}
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks_csum: NULL context");
+	rc = ecg_recover_masks(ctx, k, p, C, S, stripes, stripe_stride, masks, result, flags, stream);
+	if (rc || S == 0 || C == 0)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	rc = masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks,
+			   one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, NULL, st);
+	if (rc == 0 && src_csums != NULL && !one)
+		rc = masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks, ECG_CM_SURVIVORS,
+				   src_csums, NULL, st);
+	return rc;
+}
+
 /* Fused product + checksum parameters (ecg_kabi.h) for output cells of C
  * bytes that start on chunk boundaries.  Returns 1 when the fused kernels
  * can take the request, 0 when the caller must run the product and

@@ -156,6 +156,10 @@ int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni
 		      int64_t sj, uint64_t len);
 /* erasure set tables (ecg_recover_masks.c) */
 void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx);
+/* ecg_recover_masks's argument checks, in its order (fn: the caller's name in
+ * the message; have_ctx = 0 fails where it reports a NULL context) */
+int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t C, uint32_t S, const void *stripes,
+			    int64_t stripe_stride, const uint32_t *masks, const void *result, unsigned flags);
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);

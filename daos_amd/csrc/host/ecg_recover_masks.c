@@ -153,6 +153,32 @@ void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx)
 			}
 }
 
+/* The argument checks of ecg_recover_masks in its order, for it and for the
+ * composite ecg_recover_masks_csum (fn names the caller in the message;
+ * have_ctx = 0 fails where ecg_recover_masks reports a NULL context). */
+int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t C, uint32_t S, const void *stripes,
+			    int64_t stripe_stride, const uint32_t *masks, const void *result, unsigned flags)
+{
+	int rc = check_kp(fn, k, p);
+
+	if (rc)
+		return rc;
+	if (flags & ~ECG_RM_SPARSE)
+		return ecg_fail(-ECG_DER_INVAL, "%s: unknown flags 0x%x", fn, flags);
+	if (result == NULL || (uintptr_t)result % 8u)
+		return ecg_fail(-ECG_DER_INVAL, "%s: result must be 8-byte aligned device memory", fn);
+	if (S && (masks == NULL || (uintptr_t)masks % 4u))
+		return ecg_fail(-ECG_DER_INVAL, "%s: masks must be 4-byte aligned device memory", fn);
+	if (!have_ctx)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	if (S && C && stripes == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL stripes", fn);
+	/* the kernel reads mask words while other blocks write cells */
+	if (S && C && ecg_cells_overlap(masks, 4ull * S, stripes, S, stripe_stride, k + p, (int64_t)C, C))
+		return ecg_fail(-ECG_DER_INVAL, "%s: masks overlaps the stripes", fn);
+	return 0;
+}
+
 int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		      void *stripes, int64_t stripe_stride,
 		      const uint32_t *masks, void *result, unsigned flags, void *stream)
@@ -164,22 +190,10 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	uint32_t kid = 0;
 	int rc, e, bytewise;
 
-	rc = check_kp("recover_masks", k, p);
+	rc = ecg_recover_masks_check("recover_masks", ctx != NULL, k, p, C, S, stripes, stripe_stride, masks, result,
+				     flags);
 	if (rc)
 		return rc;
-	if (flags & ~ECG_RM_SPARSE)
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: unknown flags 0x%x", flags);
-	if (result == NULL || (uintptr_t)result % 8u)
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: result must be 8-byte aligned device memory");
-	if (S && (masks == NULL || (uintptr_t)masks % 4u))
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: masks must be 4-byte aligned device memory");
-	if (ctx == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: NULL context");
-	if (S && C && stripes == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: NULL stripes");
-	/* the kernel reads mask words while other blocks write cells */
-	if (S && C && ecg_cells_overlap(masks, 4ull * S, stripes, S, stripe_stride, k + p, (int64_t)C, C))
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks: masks overlaps the stripes");
 	rc = ecg_ctx_enter(ctx);
 	if (rc)
 		return rc;

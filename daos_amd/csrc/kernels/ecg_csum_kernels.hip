@@ -663,7 +663,250 @@ ecg_csum_mask_kernel(const uint8_t *got, const uint8_t *want, uint32_t nstripes,
 }
 constexpr uint32_t KID_MASK = KID_COMPARE + 1;
 
+// ---------------------------------------------------------------------------
+// ecg_csum_masked: the checksums of the cells each stripe's mask word selects
+// (ecg_kabi.h ecg_csum_masked_sel), a wave per (stripe, selected cell, chunk).
+// Only the geometry differs from ecg_crc_kernel / ecg_adler_kernel: item g =
+// (s * slots + r) * nch + c reads masks[s] (wave-uniform), takes the r-th set
+// bit of sel as its cell and is skipped when sel has no r-th bit, so a clean
+// stripe costs its items one load each.  Every address derives from sel, which
+// is 0 unless ecg_erasure_set_read reads the word as a set and has no bit at or
+// above k + p: all 2^32 mask values are safe.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ bool masked_geom(const ecg_csum_masked_params_t &p, uint64_t g, const uint8_t *&base,
+					    uint64_t &len, uint64_t &slot)
+{
+	const uint64_t per = (uint64_t)p.slots * p.nch;
+	uint64_t s;
+	uint32_t r, c;
+
+	if (((g | per) >> 32) == 0) {	// as chunk_geom_fast: 32-bit divisions when the counts allow
+		const uint32_t s32 = (uint32_t)g / (uint32_t)per, rem = (uint32_t)g - s32 * (uint32_t)per;
+
+		s = s32;
+		r = rem / p.nch;
+		c = rem - r * p.nch;
+	} else {
+		const uint64_t rem = g % per;
+
+		s = g / per;
+		r = (uint32_t)(rem / p.nch);
+		c = (uint32_t)(rem - (uint64_t)r * p.nch);
+	}
+	const uint32_t m = p.masks[s];
+	int valid;
+	uint32_t sel = ecg_csum_masked_sel(m, (int)p.k, (int)p.p, p.which, &valid);
+
+	if (r == 0 && c == 0 && m != 0 && p.result != nullptr && (threadIdx.x & 63) == 0) {
+		unsigned long long *res = (unsigned long long *)p.result;
+
+		if (valid) {
+			atomicAdd(&res[0], 1ull);
+			atomicAdd(&res[2], (unsigned long long)__builtin_popcount(sel));
+		} else {
+			atomicMin(&res[1], (unsigned long long)s);
+			atomicAdd(&res[3], 1ull);
+		}
+	}
+	if (r >= (uint32_t)__builtin_popcount(sel))
+		return false;
+	for (uint32_t i = 0; i < r; i++)
+		sel &= sel - 1u;
+	const uint32_t cell = (uint32_t)__builtin_ctz(sel);	// < k + p
+	const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
+
+	len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
+	base = p.src + (int64_t)s * p.stripe_stride + (uint64_t)cell * p.cell_bytes + off;
+	slot = (s * (p.k + p.p) + cell) * p.nch + c;
+	return true;
+}
+
+// One checksum of LEN bytes at slot `slot`, little-endian; the array may lie
+// at any byte, and a crc16 slot is two bytes wide: its neighbours may belong
+// to cells that are not selected.
+template <int LEN, typename T>
+__device__ __forceinline__ void masked_store(uint8_t *out, uint64_t slot, T v)
+{
+	uint8_t *at = out + slot * LEN;
+
+	if (((uintptr_t)at & (LEN - 1)) == 0) {
+		if constexpr (LEN == 2)
+			*(uint16_t *)at = (uint16_t)v;
+		else
+			*(T *)at = v;
+	} else {
+#pragma unroll
+		for (int b = 0; b < LEN; b++)
+			at[b] = (uint8_t)(v >> (8 * b));
+	}
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_kernel(ecg_csum_masked_params_t p)
+{
+	using T = typename reg<W>::T;
+	using L = crc_lds<W, TK>;
+	constexpr int NB = W / 8;
+	static_assert(TK != TK_B8, "m is a multiple of UN below");
+	__shared__ T s5[L::N5];
+	__shared__ T sl[L::NSL];
+	__shared__ T sh[L::NSL];
+	__shared__ T r4[REFL ? 16 : 1];
+	const T *gt = (const T *)p.tbl;
+
+	stage_tables<W, TK>(s5, sl, sh, gt, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
+			    ECG_CSUM_OFF_A4_4K(NB), CS_BLOCK);
+	if (REFL && threadIdx.x < 16)
+		r4[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
+	const int lane = threadIdx.x & 63;
+	const T klane = REFL ? (T)0 : gt[2 * NB * 256 + lane];
+	const T poly = (T)p.poly, init = (T)p.init, xorout = (T)p.xorout;
+	__syncthreads();
+
+	const uint64_t total = (uint64_t)p.nstripes * p.slots * p.nch;
+	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
+		uint64_t len, slot;
+		const uint8_t *base;
+
+		if (!masked_geom(p, g, base, len, slot))
+			continue;
+		const int64_t nq = (int64_t)(len / 16);
+		const int64_t m = lane_steps<TK>(nq, 64);
+		const int64_t z = m * 64 - nq;
+		T acc = 0;
+
+		if (m > 0) {
+			uint32_t d[L::UN][4];
+
+			load_step<L::UN, W, ALIGNED, true>(base, 0, 64, lane - z, m, init, d);
+			acc = horner<W, REFL, TK, L::UN>(acc, d, 0, m, s5, sl, sh);
+			for (int64_t i = L::UN; i < m; i += L::UN) {
+				load_step<L::UN, W, ALIGNED, false>(base, i, 64, lane - z, m, init, d);
+				acc = horner<W, REFL, TK, L::UN>(acc, d, i, m, s5, sl, sh);
+			}
+		}
+		acc = lane_shift<W, REFL>(acc, klane, gt, r4, (uint32_t)lane, poly);
+		acc = wave_xor_uniform(acc);
+		if (lane == 0) {
+			T crc = nq == 0 ? init : acc;
+
+			for (uint64_t b = (uint64_t)nq * 16; b < len; b++)	// tail bytes: sl[0] in memory
+				crc = byte_step<W, REFL>(crc, base[b], gt);
+			crc ^= xorout;
+			masked_store<NB>(p.out, slot, crc);
+		}
+	}
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_kernel(ecg_csum_masked_params_t p)
+{
+	const int lane = threadIdx.x & 63;
+	const uint64_t total = (uint64_t)p.nstripes * p.slots * p.nch;
+	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+
+	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
+		uint64_t len, slot;
+		const uint8_t *base;
+
+		if (!masked_geom(p, g, base, len, slot))
+			continue;
+		const uint64_t nq = len / 16;
+		uint64_t s = 0, w = 0;
+
+		for (uint64_t q = lane, it = 0; q < nq; q += 64, it++) {
+			uint32_t d[4];
+			uint32_t s16 = 0, w16 = 0;
+
+			load16<ALIGNED>(base + 16 * q, d);
+#pragma unroll
+			for (int j = 0; j < 4; j++) {
+				s16 = __builtin_amdgcn_udot4(d[j], 0x01010101u, s16, false);
+				w16 = __builtin_amdgcn_udot4(d[j], 0x03020100u + 0x04040404u * j, w16, false);
+			}
+			s += s16;
+			w += 16 * q * (uint64_t)s16 + w16;
+			if ((it & 255) == 255) {
+				s %= ADLER_MOD;
+				w %= ADLER_MOD;
+			}
+		}
+		s %= ADLER_MOD;
+		w %= ADLER_MOD;
+#pragma unroll
+		for (int sft = 32; sft >= 1; sft >>= 1) {
+			s += __shfl_xor(s, sft);
+			w += __shfl_xor(w, sft);
+		}
+		if (lane == 0) {
+			for (uint64_t b = nq * 16; b < len; b++) {
+				s += base[b];
+				w += b * (uint64_t)base[b];
+			}
+			const uint64_t A = s % ADLER_MOD;
+			const uint64_t Bp = ((len % ADLER_MOD) * A) % ADLER_MOD;
+			const uint64_t B = (Bp + ADLER_MOD - w % ADLER_MOD) % ADLER_MOD;
+			masked_store<4>(p.out, slot, (uint32_t)((B << 16) | A));
+		}
+	}
+}
+
+typedef void (*masked_fn_t)(ecg_csum_masked_params_t);
+struct masked_entry {
+	uint32_t type;
+	bool aligned;
+	masked_fn_t fn;
+	const char *name;
+};
+
+// the table kinds of g_csum: nibble tables for 16-byte aligned chunks, 5-bit
+// tables for the byte-granular variants
+const masked_entry g_masked[] = {
+	{1, true, ecg_crc_masked_kernel<16, false, true, TK_4>, "ecg_crc_masked_kernel<crc16>"},
+	{1, false, ecg_crc_masked_kernel<16, false, false, TK_5>, "ecg_crc_masked_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_masked_kernel<32, true, true, TK_4>, "ecg_crc_masked_kernel<crc32>"},
+	{2, false, ecg_crc_masked_kernel<32, true, false, TK_5>, "ecg_crc_masked_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_masked_kernel<64, true, true, TK_4>, "ecg_crc_masked_kernel<crc64>"},
+	{3, false, ecg_crc_masked_kernel<64, true, false, TK_5>, "ecg_crc_masked_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_masked_kernel<true>, "ecg_adler_masked_kernel"},
+	{7, false, ecg_adler_masked_kernel<false>, "ecg_adler_masked_kernel<bytes>"},
+};
+constexpr uint32_t N_MASKED = sizeof(g_masked) / sizeof(g_masked[0]);
+constexpr uint32_t KID_MASKED = KID_MASK + 1;
+
 } // namespace
+
+extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
+					uint32_t *kernel_id)
+{
+	const uint64_t total = (uint64_t)p->nstripes * p->slots * p->nch;
+	// the chunks of every cell start 16-byte aligned only when all four are
+	const bool aligned = (((uint64_t)(uintptr_t)p->src | (uint64_t)p->stripe_stride | p->cell_bytes |
+			       p->chunk_bytes) & 15u) == 0;
+	uint64_t blocks = (total + CS_WAVES - 1) / CS_WAVES;
+
+	if (total == 0)
+		return (int)hipSuccess;
+	if (p->k == 0 || p->k > ECG_RM_MAX_K || p->p == 0 || p->p > ECG_RM_MAX_P || p->which == 0 || p->which > 3 ||
+	    p->slots > p->k + p->p || p->masks == nullptr || p->chunk_bytes == 0 ||
+	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes)
+		return (int)hipErrorInvalidValue;
+	if (max_blocks == 0)
+		max_blocks = 256 * 16;	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
+	if (blocks > max_blocks)
+		blocks = max_blocks;
+	for (uint32_t i = 0; i < N_MASKED; i++) {
+		if (g_masked[i].type == p->type && g_masked[i].aligned == aligned) {
+			hipLaunchKernelGGL(g_masked[i].fn, dim3((uint32_t)blocks), dim3(CS_BLOCK), 0,
+					   (hipStream_t)stream, *p);
+			if (kernel_id)
+				*kernel_id = KID_MASKED + i;
+			return (int)hipGetLastError();
+		}
+	}
+	return (int)hipErrorInvalidValue;
+}
 
 extern "C" int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
 				      uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride,
@@ -717,6 +960,8 @@ extern "C" const char *ecg_k_csum_kernel_name(uint32_t id)
 		return "ecg_csum_compare_kernel";
 	if (id == KID_MASK)
 		return "ecg_csum_mask_kernel";
+	if (id >= KID_MASKED && id < KID_MASKED + N_MASKED)
+		return g_masked[id - KID_MASKED].name;
 	if (id >= ECG_KID_CSUM && id < ECG_KID_CSUM + N_CSUM)
 		return g_csum[id - ECG_KID_CSUM].name;
 	if (id >= ECG_KID_CSUM + N_CSUM && id < ECG_KID_CSUM + N_CSUM + N_SPLIT)

@@ -22,6 +22,7 @@ DER_NOSYS = 1010
 DER_IO = 2001
 DER_REC2BIG = 2013
 DER_DATA_LOSS = 2026
+DER_NOTSUPPORTED = 2037
 F_ACCUMULATE = 1
 
 u8p = C.POINTER(C.c_ubyte)
@@ -201,6 +202,10 @@ _SIGS = [
     ("ecg_csum_compare", C.c_int, [vp, C.c_int, vp, vp, C.c_uint64, vp, vp]),
     ("ecg_csum_mask", C.c_int, [vp, C.c_int, vp, vp, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                 C.c_uint32, vp, vp]),
+    ("ecg_csum_masked", C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp,
+                                  C.c_int64, vp, C.c_uint, vp, vp, C.c_uint, vp]),
+    ("ecg_recover_masks_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, vp,
+                                         C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
     ("ecg_set_csum_all_route", C.c_int, [vp, C.c_uint32]),
 ]
 
@@ -415,6 +420,7 @@ def repair_row(k: int, p: int, cell: int):
 
 
 RM_SPARSE = 0x1     # ECG_RM_SPARSE
+CM_ERASED, CM_SURVIVORS = 0x1, 0x2      # ECG_CM_ERASED, ECG_CM_SURVIVORS
 
 
 def erasure_sets(k: int, p: int) -> int:
@@ -689,6 +695,27 @@ class Context:
         checksums); the masks recover_masks() reads."""
         _chk(lib().ecg_csum_mask(self.h, htype, got, want, nstripes, ncells, nch, stripe_stride, cell_stride,
                                  first_cell, masks, stream), "csum_mask")
+
+    def csum_masked(self, htype: int, chunksize: int, rec_size: int, k: int, p: int, cell_bytes: int,
+                    nstripes: int, stripes: int, stripe_stride: int, masks: int, which: int, csums: int,
+                    result: int, flags: int = 0, stream=None):
+        """ecg_csum_masked: checksum the cells the device words masks[s] select -- which =
+        CM_ERASED the cells a valid mask names, CM_SURVIVORS the k lowest it does not, or both --
+        into their slots of csums[S][k+p][nch]; result: device memory for four uint64 (stripes
+        with a valid set, lowest stripe with an invalid mask, cells checksummed, stripes with an
+        invalid mask).  Operands as recover_masks()."""
+        _chk(lib().ecg_csum_masked(self.h, htype, chunksize, rec_size, k, p, cell_bytes, nstripes, stripes,
+                                   stripe_stride, masks, which, csums, result, flags, stream), "csum_masked")
+
+    def recover_masks_csum(self, k: int, p: int, cell_bytes: int, nstripes: int, stripes: int, stripe_stride: int,
+                           masks: int, result: int, htype: int, chunksize: int, rec_size: int, csums: int,
+                           src_csums: int | None = None, flags: int = 0, stream=None):
+        """ecg_recover_masks_csum: recover_masks(), then csum_masked(CM_ERASED) into csums and,
+        with src_csums, csum_masked(CM_SURVIVORS) into it (src_csums == csums: one array holds
+        both), on one stream.  result: recover_masks()'s."""
+        _chk(lib().ecg_recover_masks_csum(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride, masks,
+                                          result, flags, htype, chunksize, rec_size, csums, src_csums, stream),
+             "recover_masks_csum")
 
     def set_csum_all_route(self, route: int = 0):
         """Source checksums of *_csum_all: 0 measured default, 1 fused kernel, 2 two passes."""

@@ -140,6 +140,57 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 		  uint64_t stripe_stride, uint64_t cell_stride,
 		  uint32_t first_cell, uint32_t *masks, void *stream);
 
+/* Checksum only the cells each stripe's mask word names: the step after
+ * ecg_recover_masks (ecg.h), whose operands these are -- stripes [S][k+p][C] in
+ * logical cell order, stripe s at stripes + s*stripe_stride, masks device
+ * words; both read only.  With m = masks[s], and m valid when it is a set of
+ * 1 .. p cells below k + p (ecg_erasure_set_index(k, p, m) >= 0), the cells
+ * checksummed are
+ *   none                                            m not valid (0 included)
+ *   ECG_CM_ERASED     the cells m names: what ecg_recover_masks wrote
+ *   ECG_CM_SURVIVORS  the k lowest cells m does not name: what it read
+ *                     (ecg_recov_matrix's dec_idx for the set in ascending order)
+ * csums: device memory [S][k+p][nch], ecg_csum_len(type) bytes each, nch =
+ * ecg_csum_chunk_count(chunksize, rec_size, 0, cell_bytes / rec_size) -- the
+ * stripe-major layout of ecg_csum_mask (stripe_stride = (k+p)*nch, cell_stride
+ * = nch).  The nch slots of a selected cell receive its checksums, the cell
+ * taken as an extent from record index 0 as ecg_recover_csum takes it; no
+ * other byte of csums is written.  result: device memory, four uint64 (8-byte
+ * aligned): stripes with a valid set, lowest stripe whose non-zero mask is not
+ * valid (UINT64_MAX if none), cells checksummed, stripes whose non-zero mask is
+ * not valid -- with which = ECG_CM_ERASED the words ecg_recover_masks leaves
+ * for the same masks; {0, UINT64_MAX, 0, 0} when nstripes or cell_bytes is 0.
+ * k <= 16, p <= 3; which = 1, 2 or 3; cell_bytes % rec_size == 0; masks
+ * non-NULL and 4-byte aligned; csums must not overlap the stripes or the
+ * masks: otherwise -ECG_DER_INVAL (hash types other than the four above:
+ * -ECG_DER_NOTSUPPORTED).  Cells, strides and csums may lie at any byte.
+ * flags: ECG_RM_SPARSE is accepted and changes nothing (one launch shape
+ * serves dense and clean batches).  ecg_set_csum_launch caps the workgroups.
+ * Asynchronous on `stream`.  Telemetry: `launches` counts the launch;
+ * `csum_chunks` is not advanced, the count being known on the device only
+ * (result word 2 times nch). */
+#define ECG_CM_ERASED		0x1u
+#define ECG_CM_SURVIVORS	0x2u
+int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
+		    int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		    const void *stripes, int64_t stripe_stride, const uint32_t *masks,
+		    unsigned which, void *csums, void *result, unsigned flags, void *stream);
+
+/* ecg_recover_masks, then ecg_csum_masked(ECG_CM_ERASED) into csums, on one
+ * stream: rebuild of a batch with one erasure set per stripe and the checksums
+ * of the regenerated cells (daos_csummer_calc_iods after the codec,
+ * ref:src/object/srv_obj_migrate.c:1156).  src_csums != NULL: also
+ * ECG_CM_SURVIVORS into src_csums, the checksums a degraded read compares with
+ * the survivors' stored ones (ecg_csum_compare / ecg_csum_mask); src_csums ==
+ * csums is allowed (the slots are disjoint) and runs as one launch, any other
+ * overlap of the two is -ECG_DER_INVAL.  result: ecg_recover_masks's four
+ * words.  The argument errors of both halves are returned before anything is
+ * queued. */
+int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			   void *stripes, int64_t stripe_stride, const uint32_t *masks, void *result,
+			   unsigned flags, int type, uint64_t chunksize, uint64_t rec_size,
+			   void *csums, void *src_csums, void *stream);
+
 /* Route of the source checksums of ecg_encode_csum_all / ecg_recover_csum_all:
  * 0 the measured default per (hash type, k, output rows), 1 the fused kernel
  * wherever it can take the request, 2 always two passes.  Same results. */

@@ -22,6 +22,11 @@ report`).  Needs no GPU.
       the ecg_recover_masks kernels (remarks of
       ecg_recover_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
       exit 1 if one uses scratch.  NEW BASE pairs as for --repair
+  python tools/fused_resources.py --csum-masked NEW.txt BASE.txt
+      the ecg_csum_masked kernels (remarks of ecg_csum_kernels.hip from this
+      tree, NEW, and from the tree before, BASE): their table, exit 1 if one
+      uses scratch; every kernel of BASE must show identical figures in NEW
+      (exit 1 on any difference)
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -138,7 +143,40 @@ def repair_table(repair_txt, *pairs, pattern=REPAIR, what="repair"):
     return bad
 
 
+MASKED = re.compile(r"ecg_(crc|adler)_masked_kernelI(?:Li(\d+)ELb([01])E)?Lb([01])E")
+
+
+def csum_masked_table(new_txt, base_txt):
+    """Table of the ecg_csum_masked kernels in the remarks of ecg_csum_kernels.hip (new_txt), exit 1
+    on scratch; every kernel of base_txt (the same file of the tree before) compared field by
+    field with its figures in new_txt."""
+    new, base = parse_named(new_txt, ANY), parse_named(base_txt, ANY)
+    bad, n = 0, 0
+    print("| kernel | " + " | ".join(FIELDS) + " |")
+    print("|" + "---|" * (1 + len(FIELDS)))
+    for key in sorted(new):
+        m = MASKED.search(key[0])
+        if not m:
+            continue
+        n += 1
+        kind, w, _, aligned = m.groups()
+        label = f"`ecg_{kind}_masked_kernel<{'crc' + w + ',' if w else ''}{'aligned' if aligned == '1' else 'bytes'}>`"
+        v = new[key]
+        print(f"| {label} | " + " | ".join(str(v.get(f, "")) for f in FIELDS) + " |")
+        if v.get("ScratchSize [bytes/lane]") or v.get("VGPRs Spill"):
+            print(f"SCRATCH in {label}", file=sys.stderr)
+            bad = 1
+    print(f"\ncsum_masked kernels: {n}, " + ("SCRATCH USED" if bad else "none uses scratch"))
+    diff = [key[0] for key in sorted(base) if new.get(key) != base[key]]
+    for name in diff:
+        print(f"DIFF {name}: base {base.get((name, -1, -1))} new {new.get((name, -1, -1))}", file=sys.stderr)
+    print(f"{new_txt}: the {len(base)} kernels of {base_txt} compared, " + ("DIFFERENT" if diff else "identical"))
+    return bad | bool(diff) | (n == 0)
+
+
 def main():
+    if sys.argv[1] == "--csum-masked":
+        return csum_masked_table(*sys.argv[2:4])
     if sys.argv[1] == "--verify":
         return verify_table(*sys.argv[2:4])
     if sys.argv[1] == "--repair":
