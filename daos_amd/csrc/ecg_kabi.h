@@ -443,6 +443,25 @@ typedef struct ecg_csum_masked_params {
 } ecg_csum_masked_params_t;
 
 /*
+ * Per-stripe sets of updated cells (kernels/ecg_update_masks_kernels.hip,
+ * ecg_update_masks): bit j of a stripe's mask word = data cell j changed.
+ * ecg_update_mask_read is the one reading of a mask word, shared by the host
+ * and the kernels: ECG_UM_NONE for mask 0, ECG_UM_RANGE for a bit at or above
+ * k (the kernels leave such a stripe as it is and count it), else the number
+ * of cells, 1 .. k.  1 <= k <= ECG_KMAX_K (the callers check).
+ */
+#define ECG_UM_NONE 0
+#define ECG_UM_RANGE (-1)
+static inline ECG_KABI_HD int ecg_update_mask_read(uint32_t mask, int k)
+{
+	if (mask == 0)
+		return ECG_UM_NONE;
+	if ((mask >> k) != 0)	/* k <= 16 */
+		return ECG_UM_RANGE;
+	return __builtin_popcount(mask);
+}
+
+/*
  * The set table of one (k, p), device memory, built by host/
  * ecg_recover_masks.c: entry i (the set of index i) is ECG_RM_ENT_Q(k, p)
  * 16-byte words,
@@ -482,6 +501,27 @@ int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, con
 			       uint64_t *result, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
 			       void *stream, uint32_t *kernel_id);
 const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
+/* ecg_update_masks: p->src / p->src2 = the old / new cells (stripe s at +
+ * s * src_stripe_stride, the same stride for both; cell j at + j * cell_bytes,
+ * or with `packed` the cell of the mask's i-th set bit at + i * cell_bytes),
+ * p->dst = the parity (row r of stripe s at dst_cell_off[r] + s *
+ * dst_stripe_stride), p->k, p->rows = p, cell_bytes, nstripes, and p->tbl[r][j]
+ * the Cauchy parity rows for every j < k.  For every stripe whose mask reads
+ * as 1 .. k cells (ecg_update_mask_read), parity[r] ^= XOR_{j in mask}
+ * tbl[r][j] * (old_j ^ new_j).  result[0] += stripes updated, result[1] =
+ * min(result[1], lowest stripe with a bit at or above k), result[2] += cells
+ * applied, result[3] += stripes with such a bit; the host presets {0,
+ * UINT64_MAX, 0, 0}.  bytewise = 0: the 16-byte lane kernel (every address,
+ * stride and cell_bytes a multiple of 16; hipErrorInvalidValue otherwise), 1:
+ * the byte-granular kernel.  Block rows of `grp` stripes and the two grids as
+ * ecg_k_launch_recover_masks (sparse = 0: ECG_RM_DENSE_GRP and up to
+ * ECG_RM_DENSE_GRID_X column blocks; 1: 64 and ECG_REPAIR_GRID_X); cfg:
+ * grid_x / grid_y override either. */
+#define ECG_KID_UPDATE_MASKS 890u	/* ids of the update_masks kernels start here (below ECG_KID_COPY_SEGS) */
+int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint32_t *masks, uint64_t *result, int packed,
+			      int bytewise, int sparse, const ecg_launch_cfg_t *cfg, void *stream,
+			      uint32_t *kernel_id);
+const char *ecg_k_update_masks_kernel_name(uint32_t kernel_id);
 /* ecg_csum_mask (kernels/ecg_csum_kernels.hip): masks[s] |= 1u << (first_cell
  * + i) when any of the nch checksums of len (2, 4 or 8) bytes at index
  * s*stripe_stride + i*cell_stride + c differs between got and want. */

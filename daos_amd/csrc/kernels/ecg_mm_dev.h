@@ -386,6 +386,39 @@ __device__ __forceinline__ void mm_ptr_item(const ecg_mm_params_t &P, const u32x
 			st_g<G>(reinterpret_cast<uint8_t *>(a[KM + r]) + lo, outv[r]);
 }
 
+// The fold of the delta updates (ecg_ptr_kernels.hip ecg_upd_ptr_kernel,
+// ecg_update_masks_kernels.hip): acc[r] ^= tbl[r] * x for the 4 dwords of x
+// (one cell's old ^ new); tb = the column's PER_J = RM + (RM + 3) / 4 table
+// words in the product's LDS layout.
+template <int RM>
+__device__ __forceinline__ void upd_fold(const u32x4 *tb, int rows, const u32x4 x, u32x4 *acc)
+{
+	constexpr int T2V = (RM + 3) / 4;
+	u32x4 sel0, sel1, sel2, t2v[T2V];
+
+#pragma unroll
+	for (int w = 0; w < 4; w++) {
+		sel0[w] = x[w] & 0x07070707u;
+		sel1[w] = (x[w] >> 3) & 0x07070707u;
+		sel2[w] = (x[w] >> 6) & 0x03030303u;
+	}
+#pragma unroll
+	for (int q = 0; q < T2V; q++)
+		t2v[q] = tb[RM + q];
+#pragma unroll
+	for (int r = 0; r < RM; r++) {
+		if (r < rows) {
+			const u32x4 t = tb[r];
+			const uint32_t t2 = t2v[r / 4][r % 4];
+#pragma unroll
+			for (int w = 0; w < 4; w++)
+				acc[r][w] = xor3(acc[r][w], __builtin_amdgcn_perm(t[1], t[0], sel0[w]),
+						 xor3(__builtin_amdgcn_perm(t[3], t[2], sel1[w]),
+						      __builtin_amdgcn_perm(t2, t2, sel2[w]), 0u));
+		}
+	}
+}
+
 // One dword of every output row at byte offset `off` of the cells (the
 // partial last column of a G = 4 / 1 launch: the dword lies inside the cell).
 // The k loads are issued together.  Cells off a dword boundary (G = 1, and

@@ -194,35 +194,8 @@ ecg_mm_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *cells)
 // its table base (wave-uniform).
 // ---------------------------------------------------------------------------
 
-// acc[r] ^= tbl[r] * x for the 4 dwords of x (one pair's delta)
-template <int RM>
-__device__ __forceinline__ void upd_fold(const u32x4 *tb, int rows, const u32x4 x, u32x4 *acc)
-{
-	constexpr int T2V = (RM + 3) / 4;
-	u32x4 sel0, sel1, sel2, t2v[T2V];
-
-#pragma unroll
-	for (int w = 0; w < 4; w++) {
-		sel0[w] = x[w] & 0x07070707u;
-		sel1[w] = (x[w] >> 3) & 0x07070707u;
-		sel2[w] = (x[w] >> 6) & 0x03030303u;
-	}
-#pragma unroll
-	for (int q = 0; q < T2V; q++)
-		t2v[q] = tb[RM + q];
-#pragma unroll
-	for (int r = 0; r < RM; r++) {
-		if (r < rows) {
-			const u32x4 t = tb[r];
-			const uint32_t t2 = t2v[r / 4][r % 4];
-#pragma unroll
-			for (int w = 0; w < 4; w++)
-				acc[r][w] = xor3(acc[r][w], __builtin_amdgcn_perm(t[1], t[0], sel0[w]),
-						 xor3(__builtin_amdgcn_perm(t[3], t[2], sel1[w]),
-						      __builtin_amdgcn_perm(t2, t2, sel2[w]), 0u));
-		}
-	}
-}
+// (the fold of one pair's delta, upd_fold, is shared with the update_masks
+// kernels: ecg_mm_dev.h)
 
 // One whole 4 KiB column of item `it` at column offset `off` (= cbase + lane
 // offset): parity loads first, then the pairs two at a time (four cell loads

@@ -59,7 +59,9 @@ _SIGS = [
     ("ecg_recover", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, u32p, C.c_int, vp]),
     ("ecg_update", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.c_int, u32p, vp, vp, C.c_int64,
                              vp, C.c_int64, C.c_int64, vp]),
-    ("ecg_verify", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
+    ("ecg_update_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, C.c_int64, vp, C.c_int64,
+                                   C.c_int64, vp, vp, C.c_uint, vp]),
+    ("ecg_verify",C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_verify_cell", C.c_int, [C.c_uint32, C.c_int, C.c_int]),
     ("ecg_repair", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
@@ -420,6 +422,7 @@ def repair_row(k: int, p: int, cell: int):
 
 
 RM_SPARSE = 0x1     # ECG_RM_SPARSE
+UM_PACKED = 0x2     # ECG_UM_PACKED
 CM_ERASED, CM_SURVIVORS = 0x1, 0x2      # ECG_CM_ERASED, ECG_CM_SURVIVORS
 
 
@@ -618,6 +621,20 @@ class Context:
         _chk(lib().ecg_update(self.h, k, p, cell_bytes, nstripes, len(cell_idx), _u32(cell_idx), old, new,
                               upd_stripe_stride, parity, parity_cell_stride, parity_stripe_stride, stream),
              "update")
+
+    def update_masks(self, k: int, p: int, cell_bytes: int, nstripes: int, old: int, new: int,
+                     upd_stripe_stride: int, parity: int, parity_cell_stride: int, parity_stripe_stride: int,
+                     masks: int, result: int, flags: int = 0, stream=None):
+        """ecg_update_masks: update() with one set of changed cells per stripe -- bit j of the
+        device word masks[s] = data cell j of stripe s changed (what csum_mask() writes from the
+        checksums of the old and the new image); old / new: full stripe images, cell j at
+        + j*cell_bytes, or with UM_PACKED the cell of the i-th set bit at + i*cell_bytes;
+        result: device memory for four uint64 (stripes updated, lowest stripe with a bit at or
+        above k, cells applied, stripes with such a bit).  flags: UM_PACKED, RM_SPARSE (few
+        stripes have work; tuning only)."""
+        _chk(lib().ecg_update_masks(self.h, k, p, cell_bytes, nstripes, old, new, upd_stripe_stride, parity,
+                                    parity_cell_stride, parity_stripe_stride, masks, result, flags, stream),
+             "update_masks")
 
     def verify(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
                parity: int, parity_cell_stride: int, parity_stripe_stride: int, status: int, result: int,

@@ -164,6 +164,68 @@ int ecg_update(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
 	       void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
 	       void *stream);
 
+/* ecg_update with one set of updated cells PER STRIPE, in one launch: the
+ * batched form of the partial-stripe update agg_update_parity(entry, bit_map,
+ * cell_cnt) drives with its bitmap of updated cells (ref:src/object/
+ * srv_ec_aggregate.c:1006-1105; ecg_daos.h ecg_agg_update_parity is the
+ * one-stripe form), for a batch whose stripes changed different cells.  The
+ * sets are mask words in device memory, which ecg_csum_mask writes from the
+ * chunk checksums of the old and the new image (ecg_csum.h: ecg_csum_extents
+ * (old) -> ecg_csum_extents(new) -> ecg_memset(masks, 0) -> ecg_csum_mask(got =
+ * new, want = old) -> ecg_update_masks, five asynchronous calls on one stream;
+ * the masks never leave the device and the host need not know which cells
+ * changed).
+ * Parity addressed exactly as in ecg_update / ecg_encode: the client layout
+ * [p][S][C] (a padded row pitch included) and the recovery layout
+ * [S][k+p][C] with parity = stripes + k*C alike.  masks: device memory,
+ * nstripes words, 4-byte aligned, read only; bit j of masks[s] = data cell j
+ * of stripe s changed.  old_cells / new_cells: full stripe images, cell j of
+ * stripe s at old_cells + s*upd_stripe_stride + j*cell_bytes (the same for
+ * new_cells); only the cells a mask names are read, and with the recovery
+ * layout old_cells = stripes, upd_stripe_stride = (k+p)*C is a supported use
+ * (the old data and the parity interleave in one buffer).  With
+ * ECG_UM_PACKED the AGG_IOV_ODATA / AGG_IOV_DATA layout of the reference: the
+ * cell of the i-th set bit of masks[s], in ascending order, is at
+ * + s*upd_stripe_stride + i*cell_bytes.  With m = masks[s]:
+ *   m == 0                    nothing of the stripe is read or written; it is
+ *                             not counted
+ *   a bit at or above k set   nothing is written; the stripe is counted in
+ *                             result[3] and result[1]
+ *   otherwise (1..k bits)     parity[r] ^= XOR_{j in m} g[k+r][j] * (old_j ^
+ *                             new_j) for r < p: byte for byte what ecg_update(
+ *                             nupd = popcount(m), cell_idx = the set bits of m
+ *                             in ascending order, nstripes = 1) leaves for that
+ *                             stripe over the same cells, nothing else
+ * All 2^32 mask values are safe.  result (device, 4 x uint64, 8-byte aligned)
+ * = {stripes updated, lowest stripe with an invalid mask (UINT64_MAX if none),
+ * cells applied, stripes with an invalid mask}; nstripes == 0 or cell_bytes ==
+ * 0 leaves {0, UINT64_MAX, 0, 0}.  INVALID MASKS ARE REPORTED THROUGH result
+ * ONLY: the call itself returns 0.
+ * Limits: k <= 16 and p <= 8 (as ecg_update_ptrs).  -ECG_DER_INVAL for k or p
+ * beyond them, an unknown flag bit, masks NULL or not 4-byte aligned, result
+ * NULL or not 8-byte aligned (both checked for nstripes == 0 too), old_cells,
+ * new_cells or parity NULL, and masks or result lying inside the byte span of
+ * the parity.  THE CALLER'S CONTRACT, as in ecg_update: no old or new cell a
+ * mask names may overlap a parity cell of the batch (it is not checked).
+ * old_cells == new_cells is allowed and leaves every parity byte as it was.
+ * Any alignment and length: old_cells, new_cells, parity, the three strides
+ * and cell_bytes all multiples of 16 run the 16-byte lane kernel, everything
+ * else a byte-granular one.
+ * flags: ECG_UM_PACKED above.  ECG_RM_SPARSE is a tuning hint and never
+ * changes a result -- few stripes changed, so the launch uses the grid whose
+ * cost on clean stripes is one mask load per 64 of them; without it every
+ * stripe is expected to have work and a block row takes one stripe.
+ * ecg_set_launch's grid_x / grid_y override either grid; variant 2 forces the
+ * byte kernel.  Asynchronous on `stream`; no table is built or uploaded.
+ * Telemetry: ecg_get_stats' update_cells / update_bytes are NOT advanced (how
+ * many cells were applied is known on the device only: read result);
+ * `launches` counts the launch. */
+#define ECG_UM_PACKED 0x2u	/* ECG_RM_SPARSE (0x1u, below) is the other accepted flag */
+int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		     const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
+		     void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		     const uint32_t *masks, void *result, unsigned flags, void *stream);
+
 /* Parity consistency check: does the stored parity of every stripe still
  * match its stored data -- what the EC branch of the object verify path
  * answers by re-encoding into scratch parity and memcmp

@@ -27,6 +27,11 @@ report`).  Needs no GPU.
       tree, NEW, and from the tree before, BASE): their table, exit 1 if one
       uses scratch; every kernel of BASE must show identical figures in NEW
       (exit 1 on any difference)
+  python tools/fused_resources.py --update-masks UM.txt [NEW.txt BASE.txt]...
+      the ecg_update_masks kernels (remarks of
+      ecg_update_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
+      exit 1 if one uses scratch.  NEW BASE pairs as for --repair (upd_fold
+      moved into ecg_mm_dev.h)
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -111,6 +116,7 @@ def verify_table(verify_txt, product_txt=None):
 
 REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
+UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 ANY = re.compile(r"(\S+)()()")
 
 
@@ -183,6 +189,8 @@ def main():
         return repair_table(*sys.argv[2:])
     if sys.argv[1] == "--recover-masks":
         return repair_table(*sys.argv[2:], pattern=RECOVER_MASKS, what="recover_masks")
+    if sys.argv[1] == "--update-masks":
+        return repair_table(*sys.argv[2:], pattern=UPDATE_MASKS, what="update_masks")
     new = parse(sys.argv[1])
     base = parse(sys.argv[2]) if len(sys.argv) > 2 else None
     bad = 0
