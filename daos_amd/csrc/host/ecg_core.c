@@ -170,8 +170,8 @@ void ecg_ctx_destroy(ecg_ctx_t *ctx)
 	stage_free(ctx);
 	ecg_scratch_free(ctx);
 	ecg_csum_ctx_fini(ctx);
-	ecg_repair_ctx_fini(ctx);
-	ecg_recover_masks_ctx_fini(ctx);
+	ecg_ctx_kp_tables_fini(&ctx->repair_tbl[0][0], ECG_KMAX_K, ECG_KMAX_R);
+	ecg_ctx_kp_tables_fini(&ctx->rm_tbl[0][0], ECG_RM_MAX_K, ECG_RM_MAX_P);
 	ecg_tune_fini(ctx);
 	for (int i = 0; i < ctx->ndpool; i++) {
 		(void)hipStreamSynchronize(ctx->dpool[i]);
@@ -219,6 +219,73 @@ int ecg_ctx_enter(ecg_ctx_t *ctx)
 hipStream_t ecg_pick_stream(ecg_ctx_t *ctx, void *stream)
 {
 	return stream ? (hipStream_t)stream : ctx->stream;
+}
+
+int ecg_result_reset(void *result, hipStream_t st, const char *what)
+{
+	hipError_t he = hipMemsetAsync(result, 0, 32, st);
+
+	if (he == hipSuccess)
+		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
+	return he == hipSuccess ? 0 : ecg_hip_fail(he, what);
+}
+
+int ecg_launch_done(ecg_ctx_t *ctx, int e, const char *what, unsigned nlaunch, const char *name)
+{
+	ecg_trace_pop();
+	if (e != 0)
+		return ecg_hip_fail((hipError_t)e, what);
+	ECG_STAT_ADD(ctx, launches, nlaunch);
+	ecg_set_last_kernel(name);
+	return 0;
+}
+
+int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
+		      int64_t sj, uint64_t len)
+{
+	const int64_t ei = (ni - 1) * si, ej = (nj - 1) * sj;
+	const int64_t lo = (ei < 0 ? ei : 0) + (ej < 0 ? ej : 0);
+	const int64_t hi = (ei > 0 ? ei : 0) + (ej > 0 ? ej : 0);
+	const uintptr_t b0 = (uintptr_t)base + (uintptr_t)lo, b1 = (uintptr_t)base + (uintptr_t)hi + len;
+	const uintptr_t a0 = (uintptr_t)a, a1 = a0 + alen;
+
+	return a0 < b1 && b0 < a1;
+}
+
+int ecg_ctx_kp_table(ecg_ctx_t *ctx, void **slot, size_t bytes, int (*build)(void *img, const void *arg),
+		     const void *arg, const char *what, const void **out)
+{
+	int rc = 0;
+
+	pthread_mutex_lock(&ctx->lock);
+	if (*slot == NULL) {
+		void *img = calloc(1, bytes), *dev = NULL;
+		hipError_t e = hipSuccess;
+
+		rc = img ? build(img, arg) : ecg_fail(-ECG_DER_NOMEM, "%s", what);
+		if (rc == 0 && (e = hipMalloc(&dev, bytes)) == hipSuccess)
+			e = hipMemcpy(dev, img, bytes, hipMemcpyHostToDevice);
+		if (e != hipSuccess) {
+			if (dev)
+				(void)hipFree(dev);
+			rc = ecg_hip_fail(e, what);
+		} else if (rc == 0) {
+			*slot = dev;
+		}
+		free(img);
+	}
+	*out = *slot;
+	pthread_mutex_unlock(&ctx->lock);
+	return rc;
+}
+
+void ecg_ctx_kp_tables_fini(void **slots, int nk, int np)
+{
+	for (int i = 0; i < nk * np; i++)
+		if (slots[i]) {
+			(void)hipFree(slots[i]);
+			slots[i] = NULL;
+		}
 }
 
 int ecg_set_launch(ecg_ctx_t *ctx, uint32_t grid_x, uint32_t grid_y, uint32_t variant)

@@ -883,12 +883,7 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const struct masked_geom *g, 
 	prm.type = (uint32_t)type;
 	ecg_trace_push("ecg:csum_masked");
 	e = ecg_k_launch_csum_masked(&prm, (void *)st, ctx->csum_blocks, &kid);
-	ecg_trace_pop();
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "csum_masked kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "csum_masked kernel launch", 1, ecg_k_kernel_name(kid));
 }
 
 /* ECG_RM_SPARSE is accepted and ignored: the one grid serves dense and clean

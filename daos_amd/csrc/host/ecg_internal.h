@@ -86,13 +86,12 @@ struct ecg_ctx {
 	hipStream_t dpool[ECG_DROPIN_STREAMS];	/* device-cell drop-in calls (ecg_stage.c) */
 	int ndpool;
 	struct ecg_tuner *tuner;	/* blocks-per-CU cap per shape (ecg_tune.c) */
-	/* device row tables of ecg_repair by (k, p): (k + p) x k ecg_ptbl_t, built
-	 * and uploaded on first use under `lock`, kept until ecg_ctx_destroy
-	 * (ecg_repair.c) */
+	/* device tables by (k, p), built and uploaded on first use under `lock`
+	 * and kept until ecg_ctx_destroy (ecg_ctx_kp_table): the row tables of
+	 * ecg_repair, (k + p) x k ecg_ptbl_t (ecg_repair.c), and the set tables of
+	 * ecg_recover_masks, one entry per erasure set (ecg_kabi.h ECG_RM_ENT_Q,
+	 * ecg_recover_masks.c) */
 	void *repair_tbl[ECG_KMAX_K][ECG_KMAX_R];
-	/* device set tables of ecg_recover_masks by (k, p): one entry per erasure
-	 * set (ecg_kabi.h ECG_RM_ENT_Q), handled as repair_tbl is
-	 * (ecg_recover_masks.c) */
 	void *rm_tbl[ECG_RM_MAX_K][ECG_RM_MAX_P];
 	ecg_stats_t stats;		/* telemetry (ecg_get_stats), updated with atomics */
 };
@@ -148,14 +147,24 @@ void ecg_segs_fini(struct ecg_segs *v);
 /* launch over a device copy of v->seg already queued on st */
 int ecg_segs_launch(const struct ecg_segs *v, const void *segs_dev, hipStream_t st);
 
-/* repair row tables (ecg_repair.c) */
-void ecg_repair_ctx_fini(ecg_ctx_t *ctx);
+/* what ecg_verify and the mask-driven calls share (ecg_core.c) */
+/* result = {0, UINT64_MAX, 0, 0} on st, the preset of the kernels' counters
+ * (kernels/ecg_rows_dev.h rows_count); `what`: the error text ("repair memset") */
+int ecg_result_reset(void *result, hipStream_t st, const char *what);
+/* After a launch inside an ecg_trace_push range: ends the range; e != 0 (a
+ * hipError_t) fails as `what`, else nlaunch launches and the kernel's name count */
+int ecg_launch_done(ecg_ctx_t *ctx, int e, const char *what, unsigned nlaunch, const char *name);
 /* Does [a, a + alen) meet the cells base + i*si + j*sj, i < ni, j < nj, each
- * len bytes long? (ecg_repair.c) */
+ * len bytes long?  (Their bounding range: strides may be negative.) */
 int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
 		      int64_t sj, uint64_t len);
-/* erasure set tables (ecg_recover_masks.c) */
-void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx);
+/* The device table *slot (of ctx->repair_tbl or ctx->rm_tbl), built on first
+ * use under ctx->lock: build(img, arg) fills the zeroed host image, which is
+ * uploaded synchronously.  *out = the table; a failure names it as `what` and
+ * leaves the slot NULL. */
+int ecg_ctx_kp_table(ecg_ctx_t *ctx, void **slot, size_t bytes, int (*build)(void *img, const void *arg),
+		     const void *arg, const char *what, const void **out);
+void ecg_ctx_kp_tables_fini(void **slots, int nk, int np);	/* frees nk x np of them */
 /* ecg_recover_masks's argument checks, in its order (fn: the caller's name in
  * the message; have_ctx = 0 fails where it reports a NULL context) */
 int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t C, uint32_t S, const void *stripes,

@@ -53,14 +53,16 @@ int ecg_erasure_set_index(int k, int p, uint32_t mask)
 	return rc;	/* the index, or -1 for the empty set */
 }
 
-/* Host image of the (k, p) set table: every mask of at most p bits below
- * k + p fills the entry of its index. */
-static int build_sets(int k, int p, uint32_t *img, uint32_t nsets)
+/* Host image of the (k, p) set table (ecg_ctx_kp_table's build): every mask
+ * of at most p bits below k + p fills the entry of its index. */
+static int build_sets(void *image, const void *arg)
 {
+	const int k = ((const int *)arg)[0], p = ((const int *)arg)[1];
 	unsigned char en[(ECG_RM_MAX_K + ECG_RM_MAX_P) * ECG_RM_MAX_K];
 	const uint32_t entw = 4u * ECG_RM_ENT_Q(k, p), per_j = (uint32_t)p + 1u;
+	const uint32_t nsets = ecg_erasure_set_count(k, p);
 	const int n = k + p;
-	uint32_t seen = 0;
+	uint32_t *img = image, seen = 0;
 
 	ecg_gf_init();
 	ecg_gen_cauchy1(k, p, en);
@@ -105,54 +107,6 @@ static int build_sets(int k, int p, uint32_t *img, uint32_t nsets)
 	return 0;
 }
 
-/* Device copy of the (k, p) set table, built once per (k, p) and context
- * (ctx->lock); synchronous on first use. */
-static int set_table(ecg_ctx_t *ctx, int k, int p, const void **out)
-{
-	int rc = 0;
-
-	pthread_mutex_lock(&ctx->lock);
-	if (ctx->rm_tbl[k - 1][p - 1] == NULL) {
-		const uint32_t nsets = ecg_erasure_set_count(k, p);
-		const size_t bytes = (size_t)nsets * 16u * ECG_RM_ENT_Q(k, p);
-		uint32_t *img = calloc(1, bytes);
-		void *dev = NULL;
-		hipError_t e;
-
-		if (img == NULL) {
-			rc = ecg_fail(-ECG_DER_NOMEM, "recover_masks set table");
-		} else {
-			rc = build_sets(k, p, img, nsets);
-			if (rc == 0) {
-				e = hipMalloc(&dev, bytes);
-				if (e == hipSuccess)
-					e = hipMemcpy(dev, img, bytes, hipMemcpyHostToDevice);
-				if (e != hipSuccess) {
-					if (dev)
-						(void)hipFree(dev);
-					rc = ecg_hip_fail(e, "recover_masks set table");
-				} else {
-					ctx->rm_tbl[k - 1][p - 1] = dev;
-				}
-			}
-			free(img);
-		}
-	}
-	*out = ctx->rm_tbl[k - 1][p - 1];
-	pthread_mutex_unlock(&ctx->lock);
-	return rc;
-}
-
-void ecg_recover_masks_ctx_fini(ecg_ctx_t *ctx)
-{
-	for (int k = 0; k < ECG_RM_MAX_K; k++)
-		for (int p = 0; p < ECG_RM_MAX_P; p++)
-			if (ctx->rm_tbl[k][p]) {
-				(void)hipFree(ctx->rm_tbl[k][p]);
-				ctx->rm_tbl[k][p] = NULL;
-			}
-}
-
 /* The argument checks of ecg_recover_masks in its order, for it and for the
  * composite ecg_recover_masks_csum (fn names the caller in the message;
  * have_ctx = 0 fails where ecg_recover_masks reports a NULL context). */
@@ -183,10 +137,10 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		      void *stripes, int64_t stripe_stride,
 		      const uint32_t *masks, void *result, unsigned flags, void *stream)
 {
+	const int kp[2] = {k, p};
 	const void *settbl = NULL;
 	ecg_mm_params_t *prm;
 	hipStream_t st;
-	hipError_t he;
 	uint32_t kid = 0;
 	int rc, e, bytewise;
 
@@ -199,16 +153,15 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 
-	/* result = {0, UINT64_MAX, 0, 0}: nothing recovered, nothing left */
-	he = hipMemsetAsync(result, 0, 32, st);
-	if (he == hipSuccess)
-		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
-	if (he != hipSuccess)
-		return ecg_hip_fail(he, "recover_masks memset");
-	if (S == 0 || C == 0)
-		return 0;
+	/* nothing recovered, nothing left */
+	rc = ecg_result_reset(result, st, "recover_masks memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
 
-	rc = set_table(ctx, k, p, &settbl);
+	/* the set table of (k, p): synchronous on first use */
+	rc = ecg_ctx_kp_table(ctx, &ctx->rm_tbl[k - 1][p - 1],
+			      (size_t)ecg_erasure_set_count(k, p) * 16u * ECG_RM_ENT_Q(k, p), build_sets, kp,
+			      "recover_masks set table", &settbl);
 	if (rc)
 		return rc;
 	prm = calloc(1, sizeof(*prm));
@@ -227,11 +180,6 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	ecg_trace_push("ecg:recover_masks");
 	e = ecg_k_launch_recover_masks(prm, settbl, masks, (uint64_t *)result, bytewise,
 				       (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
-	ecg_trace_pop();
 	free(prm);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "recover_masks kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_recover_masks_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "recover_masks kernel launch", 1, ecg_k_recover_masks_kernel_name(kid));
 }

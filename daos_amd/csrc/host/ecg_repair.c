@@ -55,72 +55,20 @@ int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_id
 	return 0;
 }
 
-/* Device copy of the (k + p) x k row tables, built once per (k, p) and
- * context (ctx->lock); synchronous on first use. */
-static int repair_tables(ecg_ctx_t *ctx, int k, int p, const ecg_ptbl_t **out)
+/* Host image of the (k + p) x k row tables (ecg_ctx_kp_table's build). */
+static int build_rows(void *img, const void *arg)
 {
+	const int k = ((const int *)arg)[0], p = ((const int *)arg)[1];
+	unsigned char coef[ECG_KMAX_K];
+	uint32_t idx[ECG_KMAX_K];
 	int rc = 0;
 
-	pthread_mutex_lock(&ctx->lock);
-	if (ctx->repair_tbl[k - 1][p - 1] == NULL) {
-		const size_t bytes = (size_t)(k + p) * k * sizeof(ecg_ptbl_t);
-		ecg_ptbl_t *img = malloc(bytes);
-		void *dev = NULL;
-		hipError_t e;
-
-		if (img == NULL) {
-			rc = ecg_fail(-ECG_DER_NOMEM, "repair tables");
-		} else {
-			unsigned char coef[ECG_KMAX_K];
-			uint32_t idx[ECG_KMAX_K];
-
-			for (int c = 0; c < k + p && rc == 0; c++) {
-				rc = ecg_repair_row(k, p, c, coef, idx);
-				for (int j = 0; j < k && rc == 0; j++)
-					ecg_build_ptbl(coef[j], &img[c * k + j]);
-			}
-			if (rc == 0) {
-				e = hipMalloc(&dev, bytes);
-				if (e == hipSuccess)
-					e = hipMemcpy(dev, img, bytes, hipMemcpyHostToDevice);
-				if (e != hipSuccess) {
-					if (dev)
-						(void)hipFree(dev);
-					rc = ecg_hip_fail(e, "repair tables");
-				} else {
-					ctx->repair_tbl[k - 1][p - 1] = dev;
-				}
-			}
-			free(img);
-		}
+	for (int c = 0; c < k + p && rc == 0; c++) {
+		rc = ecg_repair_row(k, p, c, coef, idx);
+		for (int j = 0; j < k && rc == 0; j++)
+			ecg_build_ptbl(coef[j], (ecg_ptbl_t *)img + c * k + j);
 	}
-	*out = ctx->repair_tbl[k - 1][p - 1];
-	pthread_mutex_unlock(&ctx->lock);
 	return rc;
-}
-
-void ecg_repair_ctx_fini(ecg_ctx_t *ctx)
-{
-	for (int k = 0; k < ECG_KMAX_K; k++)
-		for (int p = 0; p < ECG_KMAX_R; p++)
-			if (ctx->repair_tbl[k][p]) {
-				(void)hipFree(ctx->repair_tbl[k][p]);
-				ctx->repair_tbl[k][p] = NULL;
-			}
-}
-
-/* Does [a, a + alen) meet the cells base + i*si + j*sj, i < ni, j < nj, each
- * len bytes long?  (Their bounding range: strides may be negative.) */
-int ecg_cells_overlap(const void *a, uint64_t alen, const void *base, int64_t ni, int64_t si, int64_t nj,
-			int64_t sj, uint64_t len)
-{
-	const int64_t ei = (ni - 1) * si, ej = (nj - 1) * sj;
-	const int64_t lo = (ei < 0 ? ei : 0) + (ej < 0 ? ej : 0);
-	const int64_t hi = (ei > 0 ? ei : 0) + (ej > 0 ? ej : 0);
-	const uintptr_t b0 = (uintptr_t)base + (uintptr_t)lo, b1 = (uintptr_t)base + (uintptr_t)hi + len;
-	const uintptr_t a0 = (uintptr_t)a, a1 = a0 + alen;
-
-	return a0 < b1 && b0 < a1;
 }
 
 int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
@@ -128,10 +76,10 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	       void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
 	       const uint32_t *status, void *result, void *stream)
 {
-	const ecg_ptbl_t *rowtbl = NULL;
+	const int kp[2] = {k, p};
+	const void *rowtbl = NULL;
 	ecg_mm_params_t *prm;
 	hipStream_t st;
-	hipError_t he;
 	uint32_t kid = 0;
 	int rc, e, r, j, bytewise;
 
@@ -156,16 +104,14 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 
-	/* result = {0, UINT64_MAX, 0, 0}: nothing repaired, nothing left */
-	he = hipMemsetAsync(result, 0, 32, st);
-	if (he == hipSuccess)
-		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
-	if (he != hipSuccess)
-		return ecg_hip_fail(he, "repair memset");
-	if (S == 0 || C == 0)
-		return 0;
+	/* nothing repaired, nothing left */
+	rc = ecg_result_reset(result, st, "repair memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
 
-	rc = repair_tables(ctx, k, p, &rowtbl);
+	/* the row tables of (k, p): synchronous on first use */
+	rc = ecg_ctx_kp_table(ctx, &ctx->repair_tbl[k - 1][p - 1], (size_t)(k + p) * k * sizeof(ecg_ptbl_t), build_rows,
+			      kp, "repair tables", &rowtbl);
 	if (rc)
 		return rc;
 	prm = calloc(1, sizeof(*prm));
@@ -190,11 +136,6 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 
 	ecg_trace_push("ecg:repair");
 	e = ecg_k_launch_repair(prm, rowtbl, status, (uint64_t *)result, bytewise, &ctx->cfg, (void *)st, &kid);
-	ecg_trace_pop();
 	free(prm);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "repair kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_repair_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "repair kernel launch", 1, ecg_k_repair_kernel_name(kid));
 }

@@ -28,7 +28,6 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
 	ecg_mm_params_t *prm;
 	hipStream_t st;
-	hipError_t he;
 	uint32_t kid = 0;
 	int rc, e, r, j, bytewise;
 
@@ -60,14 +59,10 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 
-	/* result = {0, UINT64_MAX, 0, 0}: nothing updated, no invalid mask */
-	he = hipMemsetAsync(result, 0, 32, st);
-	if (he == hipSuccess)
-		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
-	if (he != hipSuccess)
-		return ecg_hip_fail(he, "update_masks memset");
-	if (S == 0 || C == 0)
-		return 0;
+	/* nothing updated, no invalid mask */
+	rc = ecg_result_reset(result, st, "update_masks memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
 
 	prm = calloc(1, sizeof(*prm));
 	if (prm == NULL)
@@ -99,12 +94,7 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	ecg_trace_push("ecg:update_masks");
 	e = ecg_k_launch_update_masks(prm, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0, bytewise,
 				      (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
-	ecg_trace_pop();
 	free(prm);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "update_masks kernel launch");
 	/* update_cells / update_bytes stay: the count is known on the device only */
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_update_masks_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "update_masks kernel launch", 1, ecg_k_update_masks_kernel_name(kid));
 }

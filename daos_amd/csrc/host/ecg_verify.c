@@ -51,16 +51,11 @@ int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 
-	/* result = {0, UINT64_MAX, 0, 0}; every stripe clean with every data
-	 * cell still a candidate */
-	he = hipMemsetAsync(result, 0, 32, st);
-	if (he == hipSuccess)
-		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
-	if (he != hipSuccess)
-		return ecg_hip_fail(he, "verify memset");
-	if (S == 0)
-		return 0;
-	he = hipMemsetD32Async((hipDeviceptr_t)status, (int)(((1u << k) - 1u) << 8), S, st);
+	/* nothing bad; every stripe clean with every data cell still a candidate */
+	rc = ecg_result_reset(result, st, "verify memset");
+	if (rc || S == 0)
+		return rc;
+	he =hipMemsetD32Async((hipDeviceptr_t)status, (int)(((1u << k) - 1u) << 8), S, st);
 	if (he != hipSuccess)
 		return ecg_hip_fail(he, "verify status preset");
 	if (C == 0)
@@ -95,11 +90,6 @@ int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	e = ecg_k_launch_verify(prm, status, bytewise, &ctx->cfg, (void *)st, &kid);
 	if (e == 0)
 		e = ecg_k_launch_verify_summary(status, S, k, p, (uint64_t *)result, (void *)st);
-	ecg_trace_pop();
 	free(prm);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "verify kernel launch");
-	ECG_STAT_ADD(ctx, launches, 2);
-	ecg_set_last_kernel(ecg_k_verify_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "verify kernel launch", 2, ecg_k_verify_kernel_name(kid));
 }

@@ -2,11 +2,11 @@
 // (ecg_recover_masks): a rebuild batch whose stripes lost different shards, or
 // the second half of a checksum-driven scrub, in one launch.
 //
-// A block row takes `grp` consecutive stripes (1 .. 64): lane l of every wave
-// reads the mask word of the row's stripe l (one coalesced load), reads it
-// with the one reading the host shares (ecg_kabi.h ecg_erasure_set_read), and
-// a ballot leaves the stripes with a valid set as a wave-uniform 64-bit mask.
-// The block walks the set bits.  For a stripe whose mask reads as set i it
+// A block row takes `grp` consecutive stripes (1 .. 64) and walks them as
+// every mask-driven kernel does (ecg_rows_dev.h rows_scan / rows_next): a lane
+// reads a stripe's mask word with the one reading the host shares (ecg_kabi.h
+// ecg_erasure_set_read), and a ballot leaves the stripes with a valid set as a
+// wave-uniform 64-bit mask.  For a stripe whose mask reads as set i the block
 // takes entry i of the (k, p) set table the host keeps on the device (host/
 // ecg_recover_masks.c): e, the erased cells in ecg_recov_rows's output order,
 // the k survivors, and the e x k perm tables already in the product's LDS
@@ -23,46 +23,38 @@
 // a block per column when every stripe has work, grp = 64 with a few column
 // blocks striding when almost none has -- a clean batch then costs S / 64 *
 // grid.x blocks of one load each.  Column-block 0 of a row counts its stripes
-// into `result`, one lane per stripe.
+// into `result` (ecg_rows_dev.h rows_count).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../ecg_kabi.h"
 #include "ecg_mm_dev.h"
+#include "ecg_rows_dev.h"
 
 namespace {
 
-// The row's mask words: *il = this lane's reading of stripe row * grp + lane
-// (ECG_RM_NONE past the row or the batch), returned the mask of the stripes
-// to recover -- the same in every wave of the block, the words being
-// read-only for the launch.  nsets bounds the index once more (it cannot fail:
-// the reading is a bijection onto 0 .. nsets-1).
-__device__ __forceinline__ uint64_t rm_scan(const uint32_t *__restrict__ masks, uint32_t nstripes, uint32_t row,
-					    uint32_t grp, int k, int p, uint32_t nsets,
-					    const u32x4 *__restrict__ settbl, uint32_t entq,
-					    unsigned long long *result, int *il)
-{
-	const uint32_t l = threadIdx.x & 63u;
-	const uint64_t s = (uint64_t)row * grp + l;
-	int idx = ECG_RM_NONE;
+// The reader of a mask word (ecg_rows_dev.h): the index of the set the word
+// reads as, refused when it reads as none; a regenerated cell is the call's
+// unit, the e of the set's table entry.  nsets bounds the index once more (it
+// cannot fail: the reading is a bijection onto 0 .. nsets-1).
+struct rm_read {
+	const uint32_t *__restrict__ masks;
+	int k, p;
+	uint32_t nsets;
+	const u32x4 *__restrict__ settbl;
+	uint32_t entq;
+	static constexpr int none = ECG_RM_NONE;
 
-	if (l < grp && s < nstripes)
-		idx = ecg_erasure_set_read(masks[s], k, p);
-	if (idx >= (int)nsets)
-		idx = ECG_RM_RANGE;
-	if (blockIdx.x == 0 && threadIdx.x < 64 && idx != ECG_RM_NONE) {
-		if (idx >= 0) {
-			atomicAdd(&result[0], 1ull);
-			atomicAdd(&result[2], (unsigned long long)settbl[(uint64_t)idx * entq][0]);
-		} else {
-			atomicMin(&result[1], (unsigned long long)s);
-			atomicAdd(&result[3], 1ull);
-		}
+	__device__ int load(uint64_t s) const
+	{
+		const int idx = ecg_erasure_set_read(masks[s], k, p);
+
+		return idx >= (int)nsets ? ECG_RM_RANGE : idx;
 	}
-	*il = idx;
-	return __ballot(idx >= 0);
-}
+	__device__ int verdict(int idx) const { return rows_verdict(idx == ECG_RM_NONE, idx >= 0); }
+	__device__ unsigned long long units(int idx) const { return settbl[(uint64_t)idx * entq][0]; }
+};
 
 // byte j of the entry's survivor word
 __device__ __forceinline__ uint32_t rm_dec(const u32x4 &d, int j)
@@ -90,20 +82,18 @@ ecg_recover_masks_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ sett
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<16>();
 	const uint32_t entq = ECG_RM_ENT_Q(k, RM);
-	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const rm_read read = {masks, k, RM, nsets, settbl, entq};
 	int staged = -1;	// the set whose tables s_tbl holds
 
 	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
-		int il;
-		uint64_t todo = rm_scan(masks, P.nstripes, row, grp, k, RM, nsets, settbl, entq, result, &il);
+		int il, idx;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &il);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const int idx = __builtin_amdgcn_readlane(il, l);
-			const uint32_t s = row * grp + (uint32_t)l;
+			const uint32_t s = rows_next(&todo, row, grp, il, &idx);
 			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
 
-			todo &= todo - 1;
 			if (staged != idx) {
 				__syncthreads();	// the previous stripe's columns are done with s_tbl
 				if ((int)threadIdx.x < k * PER_J)
@@ -161,23 +151,21 @@ ecg_recover_masks_byte_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__
 	const int k = (int)P.k, p = (int)P.rows;
 	const int per_j = p + 1;
 	const uint32_t entq = ECG_RM_ENT_Q(k, p);
-	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const rm_read read = {masks, k, p, nsets, settbl, entq};
 
 	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
-		int il;
-		uint64_t todo = rm_scan(masks, P.nstripes, row, grp, k, p, nsets, settbl, entq, result, &il);
+		int il, idx;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &il);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const int idx = __builtin_amdgcn_readlane(il, l);
-			const uint32_t s = row * grp + (uint32_t)l;
+			const uint32_t s = rows_next(&todo, row, grp, il, &idx);
 			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
 			const u32x4 hd = ent[0];
 			const uint8_t *__restrict__ dec = reinterpret_cast<const uint8_t *>(ent + 1);
 			const int e = (int)hd[0];
 			uint8_t *sb = P.dst + (int64_t)s * P.dst_stripe_stride;
 
-			todo &= todo - 1;
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
 
@@ -242,7 +230,7 @@ extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *
 					  void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+	uint32_t gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0)
 		return (int)hipSuccess;
@@ -250,11 +238,9 @@ extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *
 	    masks == nullptr || result == nullptr || p->src != p->dst || p->src_stripe_stride != p->dst_stripe_stride)
 		return (int)hipErrorInvalidValue;
 	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
-	const uint32_t gxmax = sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X;
-	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < gxmax ? nchunk : gxmax);
-	const uint32_t nrow = p->nstripes / grp + (p->nstripes % grp != 0);
-	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (nrow < 65535 ? nrow : 65535);
 	const uint32_t nsets = ecg_erasure_set_count((int)p->k, (int)p->rows);
+
+	rows_grid(p, grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, &gx, &gy);
 
 	if (bytewise) {
 		hipLaunchKernelGGL(ecg_recover_masks_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p,

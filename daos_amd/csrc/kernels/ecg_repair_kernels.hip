@@ -2,8 +2,8 @@
 // the second half of a scrub, queued behind the check on the same stream with
 // no host round trip in between.
 //
-// A block row takes a group of 64 stripes: lane l of every wave reads the
-// status word of the group's stripe l (one coalesced load), classifies it
+// A block row takes 64 stripes and walks them as every mask-driven kernel does
+// (ecg_rows_dev.h rows_scan / rows_next): a lane reads a stripe's status word
 // with the one reading of that word the host and the summary kernel share
 // (ecg_kabi.h ecg_verify_classify), and a ballot leaves the located stripes
 // as a wave-uniform 64-bit mask -- in a batch that is almost always clean it
@@ -26,49 +26,31 @@
 // ECG_REPAIR_GRID_X columns (blocks stride over the rest), so a clean batch
 // costs ECG_REPAIR_GRID_X * S / 64 blocks of one load each whatever the cell
 // size, and a bad stripe still has ECG_REPAIR_GRID_X blocks to itself.
-// Column-block 0 of a group counts its bad stripes into `result` (one atomic
-// per repaired or left-as-it-is bad stripe, issued by the stripe's lane).
+// Column-block 0 of a group counts its bad stripes into `result`
+// (ecg_rows_dev.h rows_count).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../ecg_kabi.h"
 #include "ecg_mm_dev.h"
+#include "ecg_rows_dev.h"
 
 namespace {
 
-// result {stripes repaired, lowest bad stripe left, data cells rewritten, bad
-// stripes left} for stripe s classified c (c != -1); one thread per stripe
-__device__ __forceinline__ void repair_count(unsigned long long *result, uint32_t s, int c, int k)
-{
-	if (c >= 0) {
-		atomicAdd(&result[0], 1ull);
-		if (c < k)
-			atomicAdd(&result[2], 1ull);
-	} else {
-		atomicMin(&result[1], (unsigned long long)s);
-		atomicAdd(&result[3], 1ull);
-	}
-}
+// The reader of a status word (ecg_rows_dev.h): the classified cell c of a
+// stripe ecg_verify_classify attributes to one cell, refused when it does not;
+// a rewritten data cell is the call's unit.
+struct repair_read {
+	const uint32_t *__restrict__ status;
+	int k, p;
+	static constexpr int none = -1;	// clean
 
-#define REPAIR_GROUP 64u	// stripes per block row: one status word per lane
-
-// The group's status words: *cl = this lane's reading of stripe g * 64 + lane
-// (-1 past the batch), returned the mask of the stripes to repair -- the same
-// in every wave of the block, the words being read-only for the launch.
-__device__ __forceinline__ uint64_t repair_scan(const uint32_t *__restrict__ status, uint32_t nstripes, uint32_t g,
-						int k, int p, unsigned long long *result, int *cl)
-{
-	const uint64_t s = (uint64_t)g * REPAIR_GROUP + (threadIdx.x & 63u);
-	int c = -1;
-
-	if (s < nstripes)
-		c = ecg_verify_classify(status[s], k, p);
-	if (blockIdx.x == 0 && threadIdx.x < 64 && c != -1)
-		repair_count(result, (uint32_t)s, c, k);
-	*cl = c;
-	return __ballot(c >= 0 && c < k + p);	// the second test cannot fail (classify masks)
-}
+	__device__ int load(uint64_t s) const { return ecg_verify_classify(status[s], k, p); }
+	// the second test cannot fail (classify masks)
+	__device__ int verdict(int c) const { return rows_verdict(c == -1, c >= 0 && c < k + p); }
+	__device__ unsigned long long units(int c) const { return c < k; }
+};
 
 } // namespace
 
@@ -90,19 +72,17 @@ ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<16>();
-	const uint32_t ngroup = P.nstripes / REPAIR_GROUP + (P.nstripes % REPAIR_GROUP != 0);
+	const uint32_t ngroup = rows_count_rows(P.nstripes, 64u);
+	const repair_read read = {status, k, p};
 	int staged = -1;	// the row whose tables s_tbl holds
 
 	for (uint32_t g = blockIdx.y; g < ngroup; g += gridDim.y) {
-		int cl;
-		uint64_t todo = repair_scan(status, P.nstripes, g, k, p, result, &cl);
+		int cl, c;
+		uint64_t todo = rows_scan(P.nstripes, g, 64u, result, read, &cl);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const int c = __builtin_amdgcn_readlane(cl, l);
-			const uint32_t s = g * REPAIR_GROUP + (uint32_t)l;
+			const uint32_t s = rows_next(&todo, g, 64u, cl, &c);
 
-			todo &= todo - 1;
 			if (staged != c) {
 				__syncthreads();	// the previous stripe's columns are done with s_tbl
 				if ((int)threadIdx.x < k) {
@@ -160,18 +140,15 @@ ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ r
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const int k = (int)P.k, p = (int)P.rows;
-	const uint32_t ngroup = P.nstripes / REPAIR_GROUP + (P.nstripes % REPAIR_GROUP != 0);
+	const uint32_t ngroup = rows_count_rows(P.nstripes, 64u);
+	const repair_read read = {status, k, p};
 
 	for (uint32_t g = blockIdx.y; g < ngroup; g += gridDim.y) {
-		int cl;
-		uint64_t todo = repair_scan(status, P.nstripes, g, k, p, result, &cl);
+		int cl, c;
+		uint64_t todo = rows_scan(P.nstripes, g, 64u, result, read, &cl);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const int c = __builtin_amdgcn_readlane(cl, l);
-			const uint32_t s = g * REPAIR_GROUP + (uint32_t)l;
-
-			todo &= todo - 1;
+			const uint32_t s = rows_next(&todo, g, 64u, cl, &c);
 			const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride;
 			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
 			const uint8_t *par0 = pb + P.dst_cell_off[0];
@@ -228,17 +205,14 @@ extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *r
 				   uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+	uint32_t gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0)
 		return (int)hipSuccess;
 	if (p->k == 0 || p->k > ECG_KMAX_K || p->rows == 0 || p->rows > ECG_KMAX_R || rowtbl == nullptr ||
 	    status == nullptr || result == nullptr)
 		return (int)hipErrorInvalidValue;
-	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x
-					       : (uint32_t)(nchunk < ECG_REPAIR_GRID_X ? nchunk : ECG_REPAIR_GRID_X);
-	const uint32_t ngroup = p->nstripes / REPAIR_GROUP + (p->nstripes % REPAIR_GROUP != 0);
-	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (ngroup < 65535 ? ngroup : 65535);
+	rows_grid(p, 64u, ECG_REPAIR_GRID_X, cfg, &gx, &gy);
 
 	if (bytewise) {
 		hipLaunchKernelGGL(ecg_repair_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,

@@ -5,14 +5,13 @@
 //
 //     parity[s][r] ^= XOR_{j in masks[s]} g[k+r][j] * (old[s][j] ^ new[s][j])
 //
-// A block row takes `grp` consecutive stripes (1 .. 64), scanned as
-// ecg_recover_masks_kernels.hip's rm_scan does: lane l of every wave reads the
-// mask word of the row's stripe l (one coalesced load), reads it with the one
-// reading the host shares (ecg_kabi.h ecg_update_mask_read), and a ballot
-// leaves the stripes with work as a wave-uniform 64-bit mask.  The block walks
-// the set bits.  The perm tables of all k columns x p rows do not depend on
-// the stripe: they are staged into LDS once per block, in ecg_upd_ptr_kernel's
-// layout (PER_J = RM + (RM + 3) / 4 words per column).  Per stripe and 4 KiB
+// A block row takes `grp` consecutive stripes (1 .. 64) and walks them as
+// every mask-driven kernel does (ecg_rows_dev.h rows_scan / rows_next): a lane
+// reads a stripe's mask word with the one reading the host shares (ecg_kabi.h
+// ecg_update_mask_read), and a ballot leaves the stripes with work as a
+// wave-uniform 64-bit mask.  The perm tables of all k columns x p rows do not
+// depend on the stripe: they are staged into LDS once per block, in
+// ecg_upd_ptr_kernel's layout (PER_J = RM + (RM + 3) / 4 words).  Per 4 KiB
 // column a lane loads its 16 bytes of every parity row first, then walks the
 // mask's set bits two at a time -- four cell loads in flight -- folding each
 // delta into the rows (ecg_mm_dev.h upd_fold), and stores each parity row
@@ -26,43 +25,34 @@
 // One kernel, two grids (the launcher's choice, ECG_RM_SPARSE): grp = 1 with a
 // block per column, grp = 64 with a few column blocks striding -- a clean
 // batch then costs S / 64 * grid.x blocks of one load each.  Column-block 0 of
-// a row counts its stripes into `result`, one lane per stripe.
+// a row counts its stripes into `result` (ecg_rows_dev.h rows_count).
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "../ecg_kabi.h"
 #include "ecg_mm_dev.h"
+#include "ecg_rows_dev.h"
 
 namespace {
 
-// The row's mask words: *mw = this lane's word of stripe row * grp + lane (0
-// past the row or the batch), returned the mask of the stripes to update --
-// the same in every wave of the block, the words being read-only for the
-// launch.
-__device__ __forceinline__ uint64_t um_scan(const uint32_t *__restrict__ masks, uint32_t nstripes, uint32_t row,
-					    uint32_t grp, int k, unsigned long long *result, uint32_t *mw)
-{
-	const uint32_t l = threadIdx.x & 63u;
-	const uint64_t s = (uint64_t)row * grp + l;
-	uint32_t m = 0;
-	int n;
+// The reader of a mask word (ecg_rows_dev.h): the word itself when it names
+// 1 .. k cells, refused with a bit at or above k; an applied cell is the
+// call's unit.
+struct um_read {
+	const uint32_t *__restrict__ masks;
+	int k;
+	static constexpr uint32_t none = 0;
 
-	if (l < grp && s < nstripes)
-		m = masks[s];
-	n = ecg_update_mask_read(m, k);
-	if (blockIdx.x == 0 && threadIdx.x < 64 && n != ECG_UM_NONE) {
-		if (n > 0) {
-			atomicAdd(&result[0], 1ull);
-			atomicAdd(&result[2], (unsigned long long)n);
-		} else {
-			atomicMin(&result[1], (unsigned long long)s);
-			atomicAdd(&result[3], 1ull);
-		}
+	__device__ uint32_t load(uint64_t s) const { return masks[s]; }
+	__device__ int verdict(uint32_t m) const
+	{
+		const int n = ecg_update_mask_read(m, k);
+
+		return rows_verdict(n == ECG_UM_NONE, n > 0);
 	}
-	*mw = m;
-	return __ballot(n > 0);
-}
+	__device__ unsigned long long units(uint32_t m) const { return ecg_update_mask_read(m, k); }
+};
 
 // byte offset of the cell of column j, the i-th set bit of its mask, from the
 // stripe's old / new base
@@ -90,7 +80,8 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<16>();
-	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const um_read read = {masks, k};
 
 	for (int i = threadIdx.x; i < ECG_KMAX_K * RM; i += BLOCK) {
 		const int j = i / RM, r = i % RM;
@@ -103,18 +94,15 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 	__syncthreads();
 
 	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
-		uint32_t mw;
-		uint64_t todo = um_scan(masks, P.nstripes, row, grp, k, result, &mw);
+		uint32_t mw, m;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &mw);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)mw, l);
-			const uint32_t s = row * grp + (uint32_t)l;
+			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
 			const uint8_t *ob = P.src + (int64_t)s * P.src_stripe_stride;
 			const uint8_t *nb = P.src2 + (int64_t)s * P.src2_stripe_stride;
 			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
 
-			todo &= todo - 1;
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t off = (uint64_t)ch * CHUNK_BYTES + lo;
 				u32x4 acc[RM];
@@ -164,21 +152,19 @@ ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const int k = (int)P.k, rows = (int)P.rows;
-	const uint32_t nrow = P.nstripes / grp + (P.nstripes % grp != 0);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const um_read read = {masks, k};
 
 	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
-		uint32_t mw;
-		uint64_t todo = um_scan(masks, P.nstripes, row, grp, k, result, &mw);
+		uint32_t mw, m;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &mw);
 
 		while (todo) {
-			const int l = __ffsll((unsigned long long)todo) - 1;
-			const uint32_t m = (uint32_t)__builtin_amdgcn_readlane((int)mw, l);
-			const uint32_t s = row * grp + (uint32_t)l;
+			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
 			const uint8_t *ob = P.src + (int64_t)s * P.src_stripe_stride;
 			const uint8_t *nb = P.src2 + (int64_t)s * P.src2_stripe_stride;
 			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
 
-			todo &= todo - 1;
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
 
@@ -239,7 +225,7 @@ extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint32_
 					 void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+	uint32_t gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0)
 		return (int)hipSuccess;
@@ -248,10 +234,8 @@ extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint32_
 	    p->src_stripe_stride != p->src2_stripe_stride)
 		return (int)hipErrorInvalidValue;
 	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
-	const uint32_t gxmax = sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X;
-	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < gxmax ? nchunk : gxmax);
-	const uint32_t nrow = p->nstripes / grp + (p->nstripes % grp != 0);
-	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (nrow < 65535 ? nrow : 65535);
+
+	rows_grid(p, grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, &gx, &gy);
 
 	if (bytewise) {
 		hipLaunchKernelGGL(ecg_update_masks_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks,
