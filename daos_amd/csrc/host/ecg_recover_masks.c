@@ -17,6 +17,12 @@
  * them (ECG_RM_ENT_Q).  Built once per (k, p) and context and kept until the
  * context goes: 3 entries for EC_2P1, 1159 entries of 1056 bytes (1.2 MB)
  * for k = 16, p = 3, the largest.
+ *
+ * ecg_recover_masks_ptrs is the same launch for stripes that are not one
+ * strided image: a host table of cell addresses, staged through a scratch slot
+ * as ecg_matmul_ptrs stages its own (ecg_ptrs.c), and the cell-table kernels
+ * of the same file.  A table that is a strided image after all is handed to
+ * ecg_recover_masks.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -182,4 +188,123 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 				       (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
 	free(prm);
 	return ecg_launch_done(ctx, e, "recover_masks kernel launch", 1, ecg_k_recover_masks_kernel_name(kid));
+}
+
+/* One pass over the caller's table of S x n cell addresses, copying it into
+ * `tab` (the pinned half of a scratch slot): a NULL entry and masks or result
+ * inside a cell fail; *bits = the OR of the addresses (the lane choice);
+ * *affine = every entry is cells[0] + s * *stride + c * C, the layout of
+ * ecg_recover_masks (S == 1: any stride). */
+static int rmp_table(uint64_t *tab, void *const *cells, uint32_t S, uint32_t n, uint64_t C, const uint32_t *masks,
+		     const void *result, uint64_t *bits, int *affine, int64_t *stride)
+{
+	const uint64_t m0 = (uint64_t)(uintptr_t)masks, m1 = m0 + 4ull * S;
+	const uint64_t r0 = (uint64_t)(uintptr_t)result, r1 = r0 + 32u;
+	const uint64_t c0 = (uint64_t)(uintptr_t)cells[0];
+	const uint64_t st = S > 1 ? (uint64_t)(uintptr_t)cells[n] - c0 : (uint64_t)n * C;
+	uint64_t all = 0;
+	int aff = 1;
+
+	for (uint32_t s = 0; s < S; s++)
+		for (uint32_t c = 0; c < n; c++) {
+			const size_t i = (size_t)s * n + c;
+			const uint64_t a = (uint64_t)(uintptr_t)cells[i];
+
+			if (a == 0)
+				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: NULL cell %zu", i);
+			/* the kernel reads mask words and counts into result while
+			 * other blocks write cells */
+			if (m0 < a + C && a < m1)
+				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: masks overlaps cell %zu", i);
+			if (r0 < a + C && a < r1)
+				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: result overlaps cell %zu", i);
+			tab[i] = a;
+			all |= a;
+			aff &= a == c0 + s * st + c * C;
+		}
+	*bits = all;
+	*affine = aff;
+	*stride = (int64_t)st;
+	return 0;
+}
+
+int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+			   const uint32_t *masks, void *result, unsigned flags, void *stream)
+{
+	const int kp[2] = {k, p};
+	const uint32_t n = (uint32_t)(k + p);
+	const size_t tbytes = (size_t)S * n * sizeof(uint64_t);
+	struct ecg_scratch_slot *sc = NULL;
+	const void *settbl = NULL;
+	ecg_mm_params_t *prm;
+	uint64_t bits = 0;
+	int64_t stride = 0;
+	hipStream_t st;
+	uint32_t kid = 0;
+	int rc, e, affine = 0;
+
+	/* the checks that need no device, in ecg_recover_masks's order and
+	 * words (no stripes: the cells are checked entry by entry below) */
+	rc = ecg_recover_masks_check("recover_masks_ptrs", ctx != NULL, k, p, 0, S, NULL, 0, masks, result, flags);
+	if (rc)
+		return rc;
+	if (S && C && cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: NULL cells");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing recovered, nothing left */
+		return ecg_result_reset(result, st, "recover_masks_ptrs memset");
+
+	/* the set table of (k, p), ecg_recover_masks's: synchronous on first use */
+	rc = ecg_ctx_kp_table(ctx, &ctx->rm_tbl[k - 1][p - 1],
+			      (size_t)ecg_erasure_set_count(k, p) * 16u * ECG_RM_ENT_Q(k, p), build_sets, kp,
+			      "recover_masks set table", &settbl);
+	if (rc)
+		return rc;
+	prm = calloc(1, sizeof(*prm));
+	if (prm == NULL)
+		return ecg_fail(-ECG_DER_NOMEM, "recover_masks_ptrs: calloc");
+	prm->cell_bytes = C;
+	prm->nstripes = S;
+	prm->k = (uint32_t)k;
+	prm->rows = (uint32_t)p;
+
+	/* the table is staged as ecg_matmul_ptrs stages its own: the caller's
+	 * array is free again when this returns */
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	if (rc == 0)
+		rc = rmp_table(sc->pin, cells, S, n, C, masks, result, &bits, &affine, &stride);
+	/* ecg_recover_masks's own layout (and masks clear of the whole image, as
+	 * it demands): its launch, with no table and no dependent address loads */
+	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C)) {
+		pthread_mutex_unlock(&ctx->lock);
+		free(prm);
+		return ecg_recover_masks(ctx, k, p, C, S, cells[0], stride, masks, result, flags, stream);
+	}
+	if (rc == 0)
+		rc = ecg_result_reset(result, st, "recover_masks_ptrs memset");
+	if (rc == 0)
+		rc = ecg_table_upload(sc, tbytes, st, "recover_masks_ptrs cell table");
+	if (rc == 0) {
+		hipError_t he;
+
+		ecg_trace_push("ecg:recover_masks_ptrs");
+		e = ecg_k_launch_recover_masks_ptrs(prm, settbl, sc->dev, masks, (uint64_t *)result,
+						    ctx->cfg.variant == 2 || (bits | C) % 16u,
+						    (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
+		rc = ecg_launch_done(ctx, e, "recover_masks_ptrs kernel launch", 1,
+				     ecg_k_recover_masks_ptrs_kernel_name(kid));
+		/* the fetch (and the kernel) read the slot: the next user waits */
+		he = hipEventRecord(sc->done, st);
+		if (he == hipSuccess)
+			sc->pending = 1;
+		else if (rc == 0)
+			rc = ecg_hip_fail(he, "scratch event record");
+	}
+	pthread_mutex_unlock(&ctx->lock);
+	free(prm);
+	return rc;
 }

@@ -197,6 +197,159 @@ ecg_recover_masks_byte_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__
 }
 
 // ---------------------------------------------------------------------------
+// The same recovery over a table of cell addresses (ecg_recover_masks_ptrs):
+// cells[s * (k + p) + c] = the device address of logical cell c of stripe s,
+// for callers whose stripes are separate buffers (rebuild, the batching
+// queue's per-request stripes, a degraded read over an sgl).  Same scan, set
+// table, staging and column code; only where a stripe's cells are differs: the
+// k survivor addresses pt[dec_idx[j]] and the e destination addresses
+// pt[out_idx[r]] of the stripe's table row pt are loaded once per stripe,
+// before the column loop (wave-uniform: the set index comes from a readlane, so
+// they are scalar loads of a read-only table), and a column adds its offset.
+// The indices into the row come from the set-table entry of a validated index,
+// never from raw mask bits, so any mask value reads inside the row.
+// ---------------------------------------------------------------------------
+
+// 16-byte lanes: every table entry 16-byte aligned and C % 16 == 0 (the host
+// sends everything else to the byte kernel).
+template <int K, int RM>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, RM, 16) ? ECG_MM_WPE(K, RM, 16) : 1)
+ecg_recover_masks_ptr_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ settbl,
+			     const uint64_t *__restrict__ cells, const uint32_t *__restrict__ masks,
+			     unsigned long long *result, uint32_t grp, uint32_t nsets)
+{
+	constexpr int KM = K ? K : ECG_KMAX_K;
+	constexpr int PER_J = RM + 1;	// RM + T2V, RM <= 4
+	__shared__ u32x4 s_tbl[KM * PER_J];
+	const int k = K ? K : (int)P.k;
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const uint32_t lo = lane_off<16>();
+	const uint32_t entq = ECG_RM_ENT_Q(k, RM);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const rm_read read = {masks, k, RM, nsets, settbl, entq};
+	int staged = -1;	// the set whose tables s_tbl holds
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		int il, idx;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &il);
+
+		while (todo) {
+			const uint32_t s = rows_next(&todo, row, grp, il, &idx);
+			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
+
+			if (staged != idx) {
+				__syncthreads();	// the previous stripe's columns are done with s_tbl
+				if ((int)threadIdx.x < k * PER_J)
+					s_tbl[threadIdx.x] = ent[2 + threadIdx.x];
+				__syncthreads();
+				staged = idx;
+			}
+
+			// the set's rows, erased cells and survivors (wave-uniform), and
+			// their addresses from the stripe's table row: one dependent
+			// (scalar) load per cell and stripe, not per column
+			const u32x4 hd = ent[0], dec = ent[1];
+			const int e = (int)hd[0];
+			const uint64_t *__restrict__ pt = cells + (uint64_t)s * (uint32_t)(k + RM);
+			uint64_t base[KM + RM];
+
+#pragma unroll
+			for (int j = 0; j < KM; j++)
+				if (j < k)
+					base[j] = pt[rm_dec(dec, j)];
+#pragma unroll
+			for (int r = 0; r < RM; r++)
+				if (r < e)
+					base[KM + r] = pt[hd[1 + r]];
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+				uint64_t a[KM + RM];
+				uint32_t z = 0;
+
+#pragma unroll
+				for (int j = 0; j < KM; j++) {
+					if (j < k) {
+						a[j] = base[j] + cbase;
+						asm volatile("" : "+s"(a[j]));
+					}
+				}
+#pragma unroll
+				for (int r = 0; r < RM; r++) {
+					if (r < e) {
+						a[KM + r] = base[KM + r] + cbase;
+						asm volatile("" : "+s"(a[KM + r]));
+					}
+				}
+				asm volatile("" : "+v"(z));
+				const u32x4 *tb = s_tbl + z;
+				// a partial last column is a lane mask (C % 16 == 0 here)
+				if (cbase + CHUNK_BYTES <= C || cbase + lo + 16 <= C)
+					mm_ptr_item<KM, RM, 16>(P, tb, k, e, s, cbase, lo, a);
+			}
+		}
+	}
+}
+
+// Any alignment, any length, any k <= 16 and p <= 3: the strided byte kernel
+// with a cell's bytes at its table entry.
+__global__ void __launch_bounds__(BLOCK)
+ecg_recover_masks_ptr_byte_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ settbl,
+				  const uint64_t *__restrict__ cells, const uint32_t *__restrict__ masks,
+				  unsigned long long *result, uint32_t grp, uint32_t nsets)
+{
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const int k = (int)P.k, p = (int)P.rows;
+	const int per_j = p + 1;
+	const uint32_t entq = ECG_RM_ENT_Q(k, p);
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const rm_read read = {masks, k, p, nsets, settbl, entq};
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		int il, idx;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &il);
+
+		while (todo) {
+			const uint32_t s = rows_next(&todo, row, grp, il, &idx);
+			const u32x4 *__restrict__ ent = settbl + (uint64_t)idx * entq;
+			const u32x4 hd = ent[0];
+			const uint8_t *__restrict__ dec = reinterpret_cast<const uint8_t *>(ent + 1);
+			const int e = (int)hd[0];
+			const uint64_t *__restrict__ pt = cells + (uint64_t)s * (uint32_t)(k + p);
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+
+				for (uint64_t i = cbase + threadIdx.x; i < cbase + CHUNK_BYTES && i < C; i += BLOCK) {
+					uint32_t o[ECG_RM_MAX_P] = {0u, 0u, 0u};
+
+					for (int j = 0; j < k; j++) {
+						const uint32_t x = reinterpret_cast<const uint8_t *>(pt[dec[j]])[i];
+						const u32x4 t2 = ent[2 + j * per_j + p];
+
+#pragma unroll
+						for (int r = 0; r < ECG_RM_MAX_P; r++) {
+							if (r < e) {
+								const u32x4 t = ent[2 + j * per_j + r];
+								const ecg_ptbl_t tb = {t[0], t[1], t[2], t[3], t2[r]};
+
+								o[r] ^= gf_mul1(tb, x);
+							}
+						}
+					}
+#pragma unroll
+					for (int r = 0; r < ECG_RM_MAX_P; r++)
+						if (r < e)
+							reinterpret_cast<uint8_t *>(pt[hd[1 + r]])[i] = (uint8_t)o[r];
+				}
+			}
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
 // Dispatch
 // ---------------------------------------------------------------------------
 typedef void (*rm_fn_t)(const ecg_mm_params_t, const u32x4 *, const uint32_t *, unsigned long long *, uint32_t,
@@ -265,5 +418,79 @@ extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *
 			   (unsigned long long *)result, grp, nsets);
 	if (kernel_id)
 		*kernel_id = ECG_KID_RECOVER_MASKS + id;
+	return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------
+// Dispatch of the cell-table kernels: the instantiation rule, the two grids
+// and the byte route of ecg_k_launch_recover_masks.
+// ---------------------------------------------------------------------------
+typedef void (*rmp_fn_t)(const ecg_mm_params_t, const u32x4 *, const uint64_t *, const uint32_t *,
+			 unsigned long long *, uint32_t, uint32_t);
+
+struct rmpentry {
+	int k, rm;
+	rmp_fn_t fn;
+	const char *name;
+};
+
+#define RMPE(K_, R_) {K_, R_, ecg_recover_masks_ptr_kernel<K_, R_>, "ecg_recover_masks_ptr_kernel<" #K_ ", " #R_ ">"}
+#define RMPK(K_) RMPE(K_, 1), RMPE(K_, 2), RMPE(K_, 3)
+
+static const rmpentry g_rmp[] = {RMPK(2), RMPK(4), RMPK(8), RMPK(16), RMPK(0)};
+#define N_RMP ((uint32_t)(sizeof(g_rmp) / sizeof(g_rmp[0])))
+#define KID_RMP_BYTE (ECG_KID_RECOVER_MASKS_PTRS + N_RMP)
+
+extern "C" const char *ecg_k_recover_masks_ptrs_kernel_name(uint32_t id)
+{
+	if (id >= ECG_KID_RECOVER_MASKS_PTRS && id < ECG_KID_RECOVER_MASKS_PTRS + N_RMP)
+		return g_rmp[id - ECG_KID_RECOVER_MASKS_PTRS].name;
+	if (id == KID_RMP_BYTE)
+		return "ecg_recover_masks_ptr_byte_kernel";
+	return "?";
+}
+
+extern "C" int ecg_k_launch_recover_masks_ptrs(const ecg_mm_params_t *p, const void *settbl,
+					       const uint64_t *cells_dev, const uint32_t *masks, uint64_t *result,
+					       int bytewise, int sparse, const ecg_launch_cfg_t *cfg, void *stream,
+					       uint32_t *kernel_id)
+{
+	hipStream_t st = (hipStream_t)stream;
+	uint32_t gx, gy;
+
+	if (p->nstripes == 0 || p->cell_bytes == 0)
+		return (int)hipSuccess;
+	if (p->k == 0 || p->k > ECG_RM_MAX_K || p->rows == 0 || p->rows > ECG_RM_MAX_P || settbl == nullptr ||
+	    cells_dev == nullptr || masks == nullptr || result == nullptr)
+		return (int)hipErrorInvalidValue;
+	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
+	const uint32_t nsets = ecg_erasure_set_count((int)p->k, (int)p->rows);
+
+	rows_grid(p, grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, &gx, &gy);
+
+	if (bytewise) {
+		hipLaunchKernelGGL(ecg_recover_masks_ptr_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p,
+				   (const u32x4 *)settbl, cells_dev, masks, (unsigned long long *)result, grp, nsets);
+		if (kernel_id)
+			*kernel_id = KID_RMP_BYTE;
+		return (int)hipGetLastError();
+	}
+	// the lane kernel reads and writes dwordx4 at the cells' own addresses,
+	// which the host has found 16-byte aligned (the table is not read here)
+	if ((p->cell_bytes & 15u) != 0)
+		return (int)hipErrorInvalidValue;
+
+	uint32_t id = N_RMP;
+	for (uint32_t i = 0; i < N_RMP; i++)
+		if (g_rmp[i].rm == (int)p->rows && (g_rmp[i].k == (int)p->k || g_rmp[i].k == 0)) {
+			id = i;
+			break;
+		}
+	if (id == N_RMP)
+		return (int)hipErrorInvalidValue;
+	hipLaunchKernelGGL(g_rmp[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, (const u32x4 *)settbl, cells_dev, masks,
+			   (unsigned long long *)result, grp, nsets);
+	if (kernel_id)
+		*kernel_id = ECG_KID_RECOVER_MASKS_PTRS + id;
 	return (int)hipGetLastError();
 }

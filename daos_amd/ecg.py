@@ -69,6 +69,8 @@ _SIGS = [
     ("ecg_repair_row", C.c_int, [C.c_int, C.c_int, C.c_int, u8p, u32p]),
     ("ecg_recover_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, vp, C.c_uint,
                                     vp]),
+    ("ecg_recover_masks_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
+                                         C.c_uint, vp]),
     ("ecg_erasure_sets", C.c_int, [C.c_int, C.c_int]),
     ("ecg_erasure_set_index", C.c_int, [C.c_int, C.c_int, C.c_uint32]),
     ("ecg_matmul_ptrs", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp), vp]),
@@ -663,6 +665,15 @@ class Context:
         unrecoverable).  flags: RM_SPARSE (few stripes have work; tuning only)."""
         _chk(lib().ecg_recover_masks(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride, masks, result,
                                      flags, stream), "recover_masks")
+
+    def recover_masks_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None,
+                           masks: int, result: int, flags: int = 0, stream=None):
+        """ecg_recover_masks_ptrs: recover_masks() over a table of cell addresses --
+        cells[s*(k+p)+c]: device address of logical cell c of stripe s (or a ctypes array of
+        c_void_p, passed as it is; the library has copied it when the call returns)."""
+        arr = cells if cells is None or isinstance(cells, C.Array) else (vp * len(cells))(*cells)
+        _chk(lib().ecg_recover_masks_ptrs(self.h, k, p, cell_bytes, nstripes, arr, masks, result, flags, stream),
+             "recover_masks_ptrs")
 
     def csum_extents(self, htype: int, chunksize: int, rec_size: int, rx_idx: int, rx_nr: int, buf: int,
                      ext_stride: int, n_ext: int, csums: int, stream=None):

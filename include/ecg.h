@@ -356,6 +356,45 @@ int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_id
 int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
 		      void *stripes, int64_t stripe_stride,
 		      const uint32_t *masks, void *result, unsigned flags, void *stream);
+/* ecg_recover_masks over a TABLE OF CELL ADDRESSES, for callers whose stripes
+ * are not one strided image: rebuild's one buffer per stripe, the batching
+ * queue's one stripe pointer per request, a degraded read whose cells lie
+ * where the iovs put them.  cells: HOST array of nstripes * (k+p) device
+ * addresses; cells[s*(k+p) + c] is logical cell c of stripe s (0..k-1 data,
+ * k..k+p-1 parity), cell_bytes long, at any address.  The table is staged
+ * internally as ecg_matmul_ptrs stages its own, so the caller may overwrite or
+ * free it as soon as the call returns.
+ * masks, result, flags (ECG_RM_SPARSE) and what happens to a stripe are
+ * ecg_recover_masks's, word for word: m == 0 leaves the stripe untouched and
+ * uncounted; a bit at or above k+p or more than p bits leaves it untouched and
+ * counts it in result[3] and result[1]; any other m writes, byte for byte,
+ * what ecg_recover(err_list = the set bits ascending, nstripes = 1) writes for
+ * a contiguous copy of that stripe, and nothing else.  All 2^32 mask values
+ * are safe: every index into a stripe's table row comes from the set-table
+ * entry of a validated set index.  result = {0, UINT64_MAX, 0, 0} also for
+ * nstripes == 0 or cell_bytes == 0; UNRECOVERABLE STRIPES ARE REPORTED THROUGH
+ * result ONLY.  Limits k <= 16, p <= 3.
+ * -ECG_DER_INVAL, checked in this order: the k / p limits; an unknown flag;
+ * result NULL or not 8-byte aligned; masks NULL or not 4-byte aligned (nstripes
+ * != 0); a NULL context; cells NULL (nstripes and cell_bytes != 0); a NULL
+ * entry (the message names its index); masks (4 * nstripes bytes) or result
+ * (32 bytes) lying inside a cell ("overlaps").
+ * NOT CHECKED, THE CALLER'S CONTRACT: NO CELL THIS LAUNCH WRITES (AN ERASED
+ * CELL OF A RECOVERABLE STRIPE) MAY OVERLAP ANY OTHER CELL THE LAUNCH READS OR
+ * WRITES, AND EVERY CELL IS MEMORY OF THE CONTEXT'S DEVICE.
+ * A table in which cells[s*(k+p)+c] == cells[0] + s*stride + c*cell_bytes for
+ * one stride (one stripe whose cells are cell_bytes apart is always such a
+ * table) IS the call ecg_recover_masks(stripes = cells[0], stripe_stride =
+ * stride): no table is uploaded and ecg_last_kernel names that kernel.  Any
+ * other table runs ecg_recover_masks_ptr_kernel<K, P> (16-byte lanes) when
+ * every entry and cell_bytes are multiples of 16, and
+ * ecg_recover_masks_ptr_byte_kernel for the WHOLE launch when one is not, or
+ * with ecg_set_launch variant 2.  Asynchronous on `stream`.  Telemetry as
+ * ecg_recover_masks: recover_stripes / recover_bytes not advanced, `launches`
+ * counts the launch. */
+int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			   void *const *cells, const uint32_t *masks, void *result,
+			   unsigned flags, void *stream);
 /* The erasure sets ecg_recover_masks knows for (k, p), host only: their
  * number N = sum_{e=1..p} C(k+p, e), and the index 0..N-1 of the set `mask`
  * names (by size, then combinatorial rank C(c1,1) + C(c2,2) + C(c3,3) of its

@@ -19,9 +19,13 @@ report`).  Needs no GPU.
       kernel of which must show identical figures (mm_ptr_item moved into
       ecg_mm_dev.h; exit 1 on any difference)
   python tools/fused_resources.py --recover-masks RM.txt [NEW.txt BASE.txt]...
-      the ecg_recover_masks kernels (remarks of
-      ecg_recover_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
-      exit 1 if one uses scratch.  NEW BASE pairs as for --repair
+      the ecg_recover_masks kernels, strided and cell-table (ptr) alike
+      (remarks of ecg_recover_masks_kernels.hip), SGPRs spilled into VGPR
+      lanes listed; exit 1 if one uses scratch.  NEW BASE pairs as for
+      --repair.  With --base BASE.txt right after RM.txt (the remarks of the
+      same file from the tree before): every kernel of BASE must show
+      identical figures in RM.txt, kernels only RM.txt has are new (exit 1
+      on any difference)
   python tools/fused_resources.py --csum-masked NEW.txt BASE.txt
       the ecg_csum_masked kernels (remarks of ecg_csum_kernels.hip from this
       tree, NEW, and from the tree before, BASE): their table, exit 1 if one
@@ -115,7 +119,7 @@ def verify_table(verify_txt, product_txt=None):
 
 
 REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
-RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
+RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
 UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 ANY = re.compile(r"(\S+)()()")
 
@@ -147,6 +151,17 @@ def repair_table(repair_txt, *pairs, pattern=REPAIR, what="repair"):
         bad |= bool(diff)
         print(f"{new_txt}: {len(new)} kernels compared with {base_txt}, " + ("DIFFERENT" if diff else "identical"))
     return bad
+
+
+def kept_identical(new_txt, base_txt):
+    """Every kernel in the remarks base_txt compared field by field with its figures in new_txt."""
+    new, base = parse_named(new_txt, ANY), parse_named(base_txt, ANY)
+    diff = [key[0] for key in sorted(base) if new.get(key) != base[key]]
+    for name in diff:
+        print(f"DIFF {name}: base {base.get((name, -1, -1))} new {new.get((name, -1, -1))}", file=sys.stderr)
+    print(f"{new_txt}: the {len(base)} kernels of {base_txt} compared, " + ("DIFFERENT" if diff else "identical")
+          + f"; {len(set(new) - set(base))} kernels are new\n")
+    return int(bool(diff))
 
 
 MASKED = re.compile(r"ecg_(crc|adler)_masked_kernelI(?:Li(\d+)ELb([01])E)?Lb([01])E")
@@ -188,7 +203,11 @@ def main():
     if sys.argv[1] == "--repair":
         return repair_table(*sys.argv[2:])
     if sys.argv[1] == "--recover-masks":
-        return repair_table(*sys.argv[2:], pattern=RECOVER_MASKS, what="recover_masks")
+        args, bad = sys.argv[2:], 0
+        if len(args) >= 3 and args[1] == "--base":
+            bad = kept_identical(args[0], args[2])
+            del args[1:3]
+        return repair_table(*args, pattern=RECOVER_MASKS, what="recover_masks") | bad
     if sys.argv[1] == "--update-masks":
         return repair_table(*sys.argv[2:], pattern=UPDATE_MASKS, what="update_masks")
     new = parse(sys.argv[1])
