@@ -183,7 +183,8 @@ int ecg_update(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
  * stripe s at old_cells + s*upd_stripe_stride + j*cell_bytes (the same for
  * new_cells); only the cells a mask names are read, and with the recovery
  * layout old_cells = stripes, upd_stripe_stride = (k+p)*C is a supported use
- * (the old data and the parity interleave in one buffer).  With
+ * (the old data and the parity interleave in one buffer).  Any of the three
+ * strides may be negative (see ecg_recover_masks).  With
  * ECG_UM_PACKED the AGG_IOV_ODATA / AGG_IOV_DATA layout of the reference: the
  * cell of the i-th set bit of masks[s], in ascending order, is at
  * + s*upd_stripe_stride + i*cell_bytes.  With m = masks[s]:
@@ -231,7 +232,8 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t
  * answers by re-encoding into scratch parity and memcmp
  * (ref:src/object/obj_verify.c) -- in one read-only pass that also says which
  * cell of a bad stripe is wrong.  Operands are addressed exactly as in
- * ecg_encode (client layout and the [S][k+p][C] recovery layout alike);
+ * ecg_encode (client layout and the [S][k+p][C] recovery layout alike; the
+ * strides may be negative, see ecg_recover_masks);
  * nothing is written to `data` or `parity`.  k <= 16, p <= 8 (every DAOS EC
  * class); any alignment and length (16-byte aligned cells of a multiple of
  * 16 bytes run the 16-byte lane kernel, everything else a byte-granular one).
@@ -273,7 +275,7 @@ int ecg_verify_cell(uint32_t status, int k, int p);
  * second half of a scrub (the object verify path and the checksum scrubber):
  * ecg_verify, then ecg_repair, two asynchronous calls on one stream.
  * Operands addressed exactly as in ecg_verify / ecg_encode (client layout and
- * [S][k+p][C] alike).  status: the nstripes words an ecg_verify of the same
+ * [S][k+p][C] alike; negative strides as in ecg_recover_masks).  status: the nstripes words an ecg_verify of the same
  * operands left (device, read only; it may not overlap the cells).  For
  * stripe s with c = ecg_verify_cell(status[s], k, p):
  *   c == -1 or -2   the stripe is not touched
@@ -320,7 +322,11 @@ int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_id
  * ecg_memset(masks, 0) -> ecg_csum_mask -> ecg_recover_masks, four
  * asynchronous calls on one stream; the masks never leave the device).
  * Operands as ecg_recover's: [S][k+p][C] in logical cell order, stripe s at
- * stripes + s*stripe_stride.  masks: device memory, nstripes words, 4-byte
+ * stripes + s*stripe_stride.  The stripe and cell strides of this call and of
+ * the other mask-driven calls (ecg_verify, ecg_repair, ecg_update_masks,
+ * ecg_csum_masked, ecg_recover_masks_csum) may be negative -- an image that
+ * descends in address, stripe s below stripe s-1 -- as long as no two cells
+ * overlap.  masks: device memory, nstripes words, 4-byte
  * aligned, read only, not overlapping the stripes (-ECG_DER_INVAL); bit c of
  * masks[s] = logical cell c of stripe s is erased.  With m = masks[s]:
  *   m == 0                      the stripe is not touched and not counted

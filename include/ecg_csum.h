@@ -142,8 +142,8 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 
 /* Checksum only the cells each stripe's mask word names: the step after
  * ecg_recover_masks (ecg.h), whose operands these are -- stripes [S][k+p][C] in
- * logical cell order, stripe s at stripes + s*stripe_stride, masks device
- * words; both read only.  With m = masks[s], and m valid when it is a set of
+ * logical cell order, stripe s at stripes + s*stripe_stride (negative strides
+ * as there), masks device words; both read only.  With m = masks[s], and m valid when it is a set of
  * 1 .. p cells below k + p (ecg_erasure_set_index(k, p, m) >= 0), the cells
  * checksummed are
  *   none                                            m not valid (0 included)
