@@ -493,28 +493,26 @@ extern "C" {
  * stripe has work: the product's grid); 1: grp = 64 and at most
  * ECG_REPAIR_GRID_X column blocks (few stripes have work: a clean batch costs
  * S / 64 * grid_x blocks of one load each).  cfg: grid_x / grid_y override
- * either. */
+ * either.
+ * cells_dev == NULL: the strided image above (src == dst and equal strides,
+ * hipErrorInvalidValue otherwise).  Otherwise ecg_recover_masks_ptrs: the same
+ * recovery with the cells of stripe s at the addresses cells_dev[s * (k + p) +
+ * c], c = 0 .. k+p-1 in logical cell order (device memory, read only for the
+ * launch); p->src / dst and the strides are then unused.
+ * bytewise = 0: the 16-byte lane kernel -- strided: base, stride and cell_bytes
+ * multiples of 16; cell table: EVERY table entry 16-byte aligned (the host's
+ * check: the launcher does not read the table) and cell_bytes % 16 == 0
+ * (hipErrorInvalidValue otherwise); 1: the byte-granular kernel.
+ * ecg_k_recover_masks_kernel_name serves the ids of both layouts. */
 #define ECG_RM_DENSE_GRP 1u
 #define ECG_RM_DENSE_GRID_X 256u
-#define ECG_KID_RECOVER_MASKS 870u	/* ids of the recover_masks kernels start here (below ECG_KID_COPY_SEGS) */
-int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint32_t *masks,
-			       uint64_t *result, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
-			       void *stream, uint32_t *kernel_id);
-const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
-/* ecg_recover_masks_ptrs: the same recovery with the cells of stripe s at the
- * addresses cells_dev[s * (k + p) + c], c = 0 .. k+p-1 in logical cell order
- * (device memory, read only for the launch); p->k, p->rows = p, cell_bytes and
- * nstripes are used, p->src / dst and the strides are not.  settbl, masks,
- * result, sparse, the two grids and cfg as for ecg_k_launch_recover_masks.
- * bytewise = 0: the 16-byte lane kernel -- EVERY table entry 16-byte aligned
- * (the host's check: the launcher does not read the table) and cell_bytes % 16
- * == 0 (hipErrorInvalidValue otherwise); 1: the byte-granular kernel. */
+#define ECG_KID_RECOVER_MASKS 870u	/* ids of the strided recover_masks kernels start here (below ECG_KID_COPY_SEGS) */
 #define ECG_KID_RECOVER_MASKS_PTRS 820u	/* ids of the cell-table recover_masks kernels (820 .. 835: above the
 					 * verify kernels' 800 .. 814, below ECG_KID_REPAIR) */
-int ecg_k_launch_recover_masks_ptrs(const ecg_mm_params_t *p, const void *settbl, const uint64_t *cells_dev,
-				    const uint32_t *masks, uint64_t *result, int bytewise, int sparse,
-				    const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
-const char *ecg_k_recover_masks_ptrs_kernel_name(uint32_t kernel_id);
+int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint64_t *cells_dev,
+			       const uint32_t *masks, uint64_t *result, int bytewise, int sparse,
+			       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
+const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
 /* ecg_update_masks: p->src / p->src2 = the old / new cells (stripe s at +
  * s * src_stripe_stride, the same stride for both; cell j at + j * cell_bytes,
  * or with `packed` the cell of the mask's i-th set bit at + i * cell_bytes),

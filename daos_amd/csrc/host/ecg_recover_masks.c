@@ -139,16 +139,56 @@ int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t
 	return 0;
 }
 
+/* The set table of (k, p), one per context: synchronous on first use.  Takes
+ * ctx->lock, so it is fetched before ecg_recover_masks_ptrs locks its slot. */
+static int rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl)
+{
+	const int kp[2] = {k, p};
+
+	return ecg_ctx_kp_table(ctx, &ctx->rm_tbl[k - 1][p - 1],
+				(size_t)ecg_erasure_set_count(k, p) * 16u * ECG_RM_ENT_Q(k, p), build_sets, kp,
+				"recover_masks set table", settbl);
+}
+
+/* The launch of both calls (fn names the call in the trace range and the
+ * messages): over the strided image `stripes`, or with cells_dev over the
+ * staged cell table (stripes NULL). */
+static int rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int p, uint64_t C, uint32_t S,
+		     void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
+		     const uint32_t *masks, void *result, unsigned flags, hipStream_t st)
+{
+	const int ptrs = cells_dev != NULL;
+	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
+	uint32_t kid = 0;
+	int e;
+
+	if (prm == NULL)
+		return ecg_fail(-ECG_DER_NOMEM, "%s: calloc", fn);
+	prm->src = stripes;
+	prm->dst = stripes;
+	prm->src_stripe_stride = stripe_stride;
+	prm->dst_stripe_stride = stripe_stride;
+	prm->cell_bytes = C;
+	prm->nstripes = S;
+	prm->k = (uint32_t)k;
+	prm->rows = (uint32_t)p;
+
+	ecg_trace_push(ptrs ? "ecg:recover_masks_ptrs" : "ecg:recover_masks");
+	e = ecg_k_launch_recover_masks(prm, settbl, cells_dev, masks, (uint64_t *)result,
+				       ctx->cfg.variant == 2 || bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg,
+				       (void *)st, &kid);
+	free(prm);
+	return ecg_launch_done(ctx, e, ptrs ? "recover_masks_ptrs kernel launch" : "recover_masks kernel launch", 1,
+			       ecg_k_recover_masks_kernel_name(kid));
+}
+
 int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 		      void *stripes, int64_t stripe_stride,
 		      const uint32_t *masks, void *result, unsigned flags, void *stream)
 {
-	const int kp[2] = {k, p};
 	const void *settbl = NULL;
-	ecg_mm_params_t *prm;
 	hipStream_t st;
-	uint32_t kid = 0;
-	int rc, e, bytewise;
+	int rc;
 
 	rc = ecg_recover_masks_check("recover_masks", ctx != NULL, k, p, C, S, stripes, stripe_stride, masks, result,
 				     flags);
@@ -163,31 +203,11 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	rc = ecg_result_reset(result, st, "recover_masks memset");
 	if (rc || S == 0 || C == 0)
 		return rc;
-
-	/* the set table of (k, p): synchronous on first use */
-	rc = ecg_ctx_kp_table(ctx, &ctx->rm_tbl[k - 1][p - 1],
-			      (size_t)ecg_erasure_set_count(k, p) * 16u * ECG_RM_ENT_Q(k, p), build_sets, kp,
-			      "recover_masks set table", &settbl);
+	rc = rm_settbl(ctx, k, p, &settbl);
 	if (rc)
 		return rc;
-	prm = calloc(1, sizeof(*prm));
-	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "recover_masks: calloc");
-	prm->src = stripes;
-	prm->dst = stripes;
-	prm->src_stripe_stride = stripe_stride;
-	prm->dst_stripe_stride = stripe_stride;
-	prm->cell_bytes = C;
-	prm->nstripes = S;
-	prm->k = (uint32_t)k;
-	prm->rows = (uint32_t)p;
-	bytewise = ctx->cfg.variant == 2 || ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u;
-
-	ecg_trace_push("ecg:recover_masks");
-	e = ecg_k_launch_recover_masks(prm, settbl, masks, (uint64_t *)result, bytewise,
-				       (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
-	free(prm);
-	return ecg_launch_done(ctx, e, "recover_masks kernel launch", 1, ecg_k_recover_masks_kernel_name(kid));
+	return rm_launch(ctx, "recover_masks", settbl, k, p, C, S, stripes, stripe_stride, NULL,
+			 ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u != 0, masks, result, flags, st);
 }
 
 /* One pass over the caller's table of S x n cell addresses, copying it into
@@ -231,17 +251,14 @@ static int rmp_table(uint64_t *tab, void *const *cells, uint32_t S, uint32_t n, 
 int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
 			   const uint32_t *masks, void *result, unsigned flags, void *stream)
 {
-	const int kp[2] = {k, p};
 	const uint32_t n = (uint32_t)(k + p);
 	const size_t tbytes = (size_t)S * n * sizeof(uint64_t);
 	struct ecg_scratch_slot *sc = NULL;
 	const void *settbl = NULL;
-	ecg_mm_params_t *prm;
 	uint64_t bits = 0;
 	int64_t stride = 0;
 	hipStream_t st;
-	uint32_t kid = 0;
-	int rc, e, affine = 0;
+	int rc, affine = 0;
 
 	/* the checks that need no device, in ecg_recover_masks's order and
 	 * words (no stripes: the cells are checked entry by entry below) */
@@ -257,19 +274,9 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (S == 0 || C == 0)	/* nothing recovered, nothing left */
 		return ecg_result_reset(result, st, "recover_masks_ptrs memset");
 
-	/* the set table of (k, p), ecg_recover_masks's: synchronous on first use */
-	rc = ecg_ctx_kp_table(ctx, &ctx->rm_tbl[k - 1][p - 1],
-			      (size_t)ecg_erasure_set_count(k, p) * 16u * ECG_RM_ENT_Q(k, p), build_sets, kp,
-			      "recover_masks set table", &settbl);
+	rc = rm_settbl(ctx, k, p, &settbl);	/* ecg_recover_masks's */
 	if (rc)
 		return rc;
-	prm = calloc(1, sizeof(*prm));
-	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "recover_masks_ptrs: calloc");
-	prm->cell_bytes = C;
-	prm->nstripes = S;
-	prm->k = (uint32_t)k;
-	prm->rows = (uint32_t)p;
 
 	/* the table is staged as ecg_matmul_ptrs stages its own: the caller's
 	 * array is free again when this returns */
@@ -281,7 +288,6 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	 * it demands): its launch, with no table and no dependent address loads */
 	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C)) {
 		pthread_mutex_unlock(&ctx->lock);
-		free(prm);
 		return ecg_recover_masks(ctx, k, p, C, S, cells[0], stride, masks, result, flags, stream);
 	}
 	if (rc == 0)
@@ -291,12 +297,8 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (rc == 0) {
 		hipError_t he;
 
-		ecg_trace_push("ecg:recover_masks_ptrs");
-		e = ecg_k_launch_recover_masks_ptrs(prm, settbl, sc->dev, masks, (uint64_t *)result,
-						    ctx->cfg.variant == 2 || (bits | C) % 16u,
-						    (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
-		rc = ecg_launch_done(ctx, e, "recover_masks_ptrs kernel launch", 1,
-				     ecg_k_recover_masks_ptrs_kernel_name(kid));
+		rc = rm_launch(ctx, "recover_masks_ptrs", settbl, k, p, C, S, NULL, 0, sc->dev, (bits | C) % 16u != 0,
+			       masks, result, flags, st);
 		/* the fetch (and the kernel) read the slot: the next user waits */
 		he = hipEventRecord(sc->done, st);
 		if (he == hipSuccess)
@@ -305,6 +307,5 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 			rc = ecg_hip_fail(he, "scratch event record");
 	}
 	pthread_mutex_unlock(&ctx->lock);
-	free(prm);
 	return rc;
 }
