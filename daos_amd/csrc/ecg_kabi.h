@@ -28,6 +28,7 @@
 #ifndef ECG_KABI_H
 #define ECG_KABI_H
 
+#include <assert.h>	/* static_assert in C */
 #include <stdint.h>
 
 #define ECG_KMAX_K 16	/* data cells per launch; host splits larger k */
@@ -36,6 +37,24 @@
 typedef struct ecg_ptbl {
 	uint32_t t0lo, t0hi, t1lo, t1hi, t2;
 } ecg_ptbl_t;
+
+/*
+ * The table layout of a product with rm output rows, as 16-byte words: the
+ * one every GF kernel stages into LDS and the set table of ecg_recover_masks
+ * stores.  Cell-major; source cell j owns ECG_TBL_PER_J(rm) words,
+ *   word  j*PER_J + r           row r's {t0lo, t0hi, t1lo, t1hi}      r < rm
+ *   words j*PER_J + rm ..       the rows' t2, four to a word: row r's is
+ *                               dword r of them
+ * so a lane reads one row with one 16-byte load and the t2 of every row with
+ * (rm + 3) / 4 more.  ECG_TBL_ROW: the word of (j, r); ECG_TBL_T2: the dword
+ * index of its t2 (both from the table's start); ECG_TBL_WORDS: the words of
+ * km cells.  The kernels go through ecg_mm_dev.h mm_tbl / tbl_stage, the
+ * host's set-table build through these macros.
+ */
+#define ECG_TBL_PER_J(rm) ((rm) + ((rm) + 3) / 4)
+#define ECG_TBL_WORDS(km, rm) ((km) * ECG_TBL_PER_J(rm))
+#define ECG_TBL_ROW(rm, j, r) ((j) * ECG_TBL_PER_J(rm) + (r))
+#define ECG_TBL_T2(rm, j, r) (4 * ECG_TBL_ROW(rm, j, rm) + (r))
 
 typedef struct ecg_mm_params {
 	const uint8_t *src;		/* cell bases (stripe 0) */
@@ -468,13 +487,15 @@ static inline ECG_KABI_HD int ecg_update_mask_read(uint32_t mask, int k)
  *   word 0      {e, out_idx[0], out_idx[1], out_idx[2]}: the erased cells in the
  *               order ecg_recov_rows writes them (unused slots 0)
  *   word 1      dec_idx[j] in byte j: the k survivors the rows read
- *   words 2..   the e x k perm tables in the product's LDS layout for RM = p
- *               output rows (ecg_mm_dev.h mm_compute: PER_J = p + 1 words per
- *               source j -- row r's {t0lo, t0hi, t1lo, t1hi} in word j*PER_J + r,
- *               its t2 in dword r of word j*PER_J + p), rows >= e zero
- * so a block stages a set with one 16-byte copy per thread.
+ *   words 2..   the e x k perm tables in the product's layout for p output
+ *               rows (ECG_TBL_PER_J above), rows >= e zero
+ * so a block stages a set with one 16-byte copy per thread.  With p <=
+ * ECG_RM_MAX_P = 3 a cell takes p + 1 words: 2 + k * (p + 1) in all.
  */
-#define ECG_RM_ENT_Q(k, p) (2u + (uint32_t)(k) * ((uint32_t)(p) + 1u))
+#define ECG_RM_ENT_Q(k, p) (2u + ECG_TBL_WORDS((uint32_t)(k), (uint32_t)(p)))
+static_assert(ECG_RM_ENT_Q(16, 1) == 2u + 16u * 2u && ECG_RM_ENT_Q(16, 2) == 2u + 16u * 3u &&
+		      ECG_RM_ENT_Q(16, ECG_RM_MAX_P) == 2u + 16u * 4u,
+	      "set-table entry: p + 1 words per cell");
 
 #ifdef __cplusplus
 extern "C" {

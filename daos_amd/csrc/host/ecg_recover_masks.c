@@ -65,7 +65,7 @@ static int build_sets(void *image, const void *arg)
 {
 	const int k = ((const int *)arg)[0], p = ((const int *)arg)[1];
 	unsigned char en[(ECG_RM_MAX_K + ECG_RM_MAX_P) * ECG_RM_MAX_K];
-	const uint32_t entw = 4u * ECG_RM_ENT_Q(k, p), per_j = (uint32_t)p + 1u;
+	const uint32_t entw = 4u * ECG_RM_ENT_Q(k, p);
 	const uint32_t nsets = ecg_erasure_set_count(k, p);
 	const int n = k + p;
 	uint32_t *img = image, seen = 0;
@@ -92,18 +92,17 @@ static int build_sets(void *image, const void *arg)
 		for (int r = 0; r < e; r++)
 			ent[1 + r] = out_idx[r];
 		for (int j = 0; j < k; j++) {
-			uint32_t *tj = ent + 8 + 4u * per_j * (uint32_t)j;
-
 			((unsigned char *)(ent + 4))[j] = (unsigned char)dec_idx[j];
 			for (int r = 0; r < e; r++) {
+				uint32_t *tw = ent + 8 + 4 * ECG_TBL_ROW(p, j, r);
 				ecg_ptbl_t t;
 
 				ecg_build_ptbl(rows[r * k + j], &t);
-				tj[4 * r + 0] = t.t0lo;
-				tj[4 * r + 1] = t.t0hi;
-				tj[4 * r + 2] = t.t1lo;
-				tj[4 * r + 3] = t.t1hi;
-				tj[4 * p + r] = t.t2;
+				tw[0] = t.t0lo;
+				tw[1] = t.t0hi;
+				tw[2] = t.t1lo;
+				tw[3] = t.t1hi;
+				ent[8 + ECG_TBL_T2(p, j, r)] = t.t2;
 			}
 		}
 		seen++;

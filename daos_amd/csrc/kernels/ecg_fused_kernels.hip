@@ -236,9 +236,7 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 	// fold one column late; not with SRC, whose source folds are already
 	// independent work next to the product and which needs the registers
 	constexpr bool DEFER = !SRC && (ECG_FUSED_DEFER & (W == 64 ? 2 : 1)) != 0;
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
-	__shared__ u32x4 s_tbl[KM * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, RM)];
 	// CRC tables (TB): 0 5-bit (conflict-free, ecg_kabi.h: positional p5 of
 	// 0..U-1 columns + a5 shift by U columns, U = ECG_MMCS_P5U); 1 byte
 	// tables sl (slice-by-NB, register folded) + the a5 4 KiB shift
@@ -319,8 +317,8 @@ ecg_mm_csum_kernel(const ecg_mm_params_t P, const ecg_mmcs_params_t Q)
 		if (q * BLOCK + (int)threadIdx.x < NST)
 			*st_dst(q * BLOCK + (int)threadIdx.x) = sv[q];
 	if (tst) {
-		s_tbl[tj * PER_J + tr] = (u32x4){tv.t0lo, tv.t0hi, tv.t1lo, tv.t1hi};
-		reinterpret_cast<uint32_t *>(&s_tbl[tj * PER_J + RM])[tr] = tv.t2;
+		s_tbl[ECG_TBL_ROW(RM, tj, tr)] = (u32x4){tv.t0lo, tv.t0hi, tv.t1lo, tv.t1hi};
+		reinterpret_cast<uint32_t *>(&s_tbl[ECG_TBL_ROW(RM, tj, RM)])[tr] = tv.t2;
 	}
 	__syncthreads();
 

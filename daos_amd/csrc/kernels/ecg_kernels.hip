@@ -32,9 +32,9 @@
 // K, R: compile-time data cells / output rows (0 = runtime, bounded by the
 // ECG_KMAX_* maxima).  ACC: XOR into dst.  DIFF: source = src ^ src2.
 //
-// Perm tables are staged once per block from the kernel arguments into LDS,
-// cell-major: for cell j, RM x {t0lo,t0hi,t1lo,t1hi} then the rows' t2 words
-// packed 4 per 16 B.  They are re-read (wave-uniform address -> broadcast,
+// Perm tables are staged once per block from the kernel arguments into LDS
+// (ecg_mm_dev.h tbl_stage; cell-major, the layout: ecg_kabi.h ECG_TBL_PER_J).
+// They are re-read (wave-uniform address -> broadcast,
 // conflict-free ds_read_b128) right before cell j is consumed.  Holding them
 // in registers instead costs 5 x k x rows dwords: that overflows the SGPR
 // file at EC_8P2 (the compiler then spills through v_writelane/v_readlane)
@@ -48,24 +48,14 @@ ecg_mm_kernel(const ecg_mm_params_t P)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int T2V = (RM + 3) / 4;		// u32x4 holding t2 of all rows
-	constexpr int PER_J = RM + T2V;			// u32x4 per cell
-	__shared__ u32x4 s_tbl[KM * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, RM)];
 	const int k = K ? K : (int)P.k;
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<G>();
 
-	for (int i = threadIdx.x; i < KM * RM; i += BLOCK) {
-		const int j = i / RM, r = i % RM;
-		if (j < k && r < rows) {
-			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
-		}
-	}
-	__syncthreads();
+	tbl_stage<RM>(s_tbl, P, KM, k, rows);
 
 	if (P.order) {
 		// 1D grid over the S x nchunk (stripe, column) items in the order
@@ -119,23 +109,13 @@ __global__ void __launch_bounds__(BLOCK)
 ecg_mm_sel_kernel(const ecg_mm_params_t P, const uint8_t *__restrict__ sel, uint32_t ncols)
 {
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
-	__shared__ u32x4 s_tbl[ECG_KMAX_K * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, RM)];
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = threadIdx.x * 16u;
 
-	for (int i = threadIdx.x; i < ECG_KMAX_K * RM; i += BLOCK) {
-		const int j = i / RM, r = i % RM;
-		if (j < (int)ncols && r < rows) {
-			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
-		}
-	}
-	__syncthreads();
+	tbl_stage<RM>(s_tbl, P, ECG_KMAX_K, (int)ncols, rows);
 
 	for (uint32_t s = blockIdx.y; s < P.nstripes; s += gridDim.y) {
 		const uint32_t j = sel[s];
@@ -147,7 +127,7 @@ ecg_mm_sel_kernel(const ecg_mm_params_t P, const uint8_t *__restrict__ sel, uint
 			uint32_t z = 0;
 
 			asm volatile("" : "+v"(z));
-			const u32x4 *tb = s_tbl + j * PER_J + z;
+			const u32x4 *tb = mm_tbl<RM>::cell(s_tbl, j) + z;
 
 			if (cbase + CHUNK_BYTES <= C)
 				mm_item<1, RM, false, false>(P, tb, 1, rows, s, cbase, lo);
@@ -443,11 +423,7 @@ extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cf
 	else if (variant == 0 && g < 16 && !(cfg && cfg->no_unaligned) && src_off16(p) && has_g2(p))
 		g = 2;		// k = 8, sources off a 16-byte boundary: funnel-shifted 16-byte lanes
 	if (variant == 2 || g == 0) {
-		uint64_t total = p->cell_bytes * p->nstripes;
-		uint64_t blocks = (total + BLOCK - 1) / BLOCK;
-		if (blocks > 8192)
-			blocks = 8192;
-		hipLaunchKernelGGL(ecg_mm_byte_kernel, dim3((uint32_t)blocks), dim3(BLOCK), 0, st, *p);
+		hipLaunchKernelGGL(ecg_mm_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p);
 		if (kernel_id)
 			*kernel_id = KID_BYTE;
 		return (int)hipGetLastError();
@@ -492,8 +468,9 @@ extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cf
 			*kernel_id = id;
 		return (int)hipGetLastError();
 	}
-	uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < 65535 ? nchunk : 65535);
-	uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (p->nstripes < 65535 ? p->nstripes : 65535);
+	uint32_t gx, gy;
+
+	mm_grid(p, cfg, &gx, &gy);
 	const size_t lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_kernels[id].k, g_kernels[id].r);
 	if (p->order) {
 		ecg_mm_params_t q = *p;
@@ -538,15 +515,14 @@ extern "C" int ecg_k_launch_copy(const void *src, void *dst, uint64_t bytes, int
 extern "C" int ecg_k_launch_matmul_sel(const ecg_mm_params_t *p, const uint8_t *sel_dev, uint32_t ncols,
 				      void *stream, uint32_t *kernel_id)
 {
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+	uint32_t gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
 		return (int)hipSuccess;
 	if (!aligned16(p) || p->k != 1 || p->accumulate || p->diff || ncols == 0 || ncols > ECG_KMAX_K ||
 	    p->rows > ECG_KMAX_R)
 		return (int)hipErrorInvalidValue;
-	uint32_t gx = (uint32_t)(nchunk < 65535 ? nchunk : 65535);
-	uint32_t gy = p->nstripes < 65535 ? p->nstripes : 65535;
+	mm_grid(p, nullptr, &gx, &gy);
 	// the DAOS classes' p = 1, 2 specialised; 3..8 parity rows runtime-shaped
 	const uint32_t v = p->rows == 1 ? 0 : p->rows == 2 ? 1 : 2;
 	if (v == 0)

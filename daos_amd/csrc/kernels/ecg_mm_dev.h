@@ -1,7 +1,10 @@
 // ecg_mm_dev.h -- device building blocks of the GF(2^8) product shared by
 // the product kernels (ecg_kernels.hip) and the fused product + checksum
 // kernels (ecg_fused_kernels.hip): lane layouts, cell loads and stores, the
-// v_perm_b32 multiply, ragged tails.  Design notes: ecg_kernels.hip header.
+// perm tables in LDS (mm_tbl, tbl_stage; the layout itself: ecg_kabi.h
+// ECG_TBL_PER_J), the v_perm_b32 multiply, the scalar fold of the partial
+// columns (gf_fold_dword / gf_fold_byte), ragged tails.  Design notes:
+// ecg_kernels.hip header, DESIGN.md §25.
 #ifndef ECG_MM_DEV_H
 #define ECG_MM_DEV_H
 
@@ -186,6 +189,80 @@ __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c)
 	return __builtin_amdgcn_bitop3_b32(a, b, c, 0x96);
 }
 
+// The perm tables of a product with RM output rows as the kernels keep them
+// in LDS (the layout: ecg_kabi.h ECG_TBL_PER_J).  tb = the table's first word.
+template <int RM>
+struct mm_tbl {
+	static constexpr int PER_J = ECG_TBL_PER_J(RM);	// u32x4 per cell
+	static constexpr int T2V = PER_J - RM;		// u32x4 holding t2 of all rows
+
+	// cell j's PER_J words
+	static __device__ __forceinline__ const u32x4 *cell(const u32x4 *tb, int j) { return tb + ECG_TBL_ROW(RM, j, 0); }
+	// {t0lo, t0hi, t1lo, t1hi} of (cell j, row r)
+	static __device__ __forceinline__ u32x4 row(const u32x4 *tb, int j, int r) { return tb[ECG_TBL_ROW(RM, j, r)]; }
+	static __device__ __forceinline__ uint32_t t2(const u32x4 *tb, int j, int r)
+	{
+		return reinterpret_cast<const uint32_t *>(&tb[ECG_TBL_ROW(RM, j, RM)])[r];
+	}
+	// word q < T2V of cell j's t2 words: row r's t2 is t2w(r / 4)[r % 4]
+	static __device__ __forceinline__ u32x4 t2w(const u32x4 *tb, int j, int q) { return tb[ECG_TBL_ROW(RM, j, RM + q)]; }
+	static __device__ __forceinline__ ecg_ptbl_t entry(const u32x4 *tb, int j, int r)
+	{
+		const u32x4 t = row(tb, j, r);
+
+		return (ecg_ptbl_t){t[0], t[1], t[2], t[3], t2(tb, j, r)};
+	}
+	static __device__ __forceinline__ void put(u32x4 *tb, int j, int r, const ecg_ptbl_t &t)
+	{
+		tb[ECG_TBL_ROW(RM, j, r)] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
+		reinterpret_cast<uint32_t *>(&tb[ECG_TBL_ROW(RM, j, RM)])[r] = t.t2;
+	}
+};
+
+// Stage P.tbl[r][j], r < rows, j < ncols, into the block's s_tbl of km cells,
+// and wait for it.
+template <int RM>
+__device__ __forceinline__ void tbl_stage(u32x4 *s_tbl, const ecg_mm_params_t &P, int km, int ncols, int rows)
+{
+	for (int i = threadIdx.x; i < km * RM; i += BLOCK) {
+		const int j = i / RM, r = i % RM;
+		if (j < ncols && r < rows)
+			mm_tbl<RM>::put(s_tbl, j, r, P.tbl[r][j]);
+	}
+	__syncthreads();
+}
+
+// The scalar fold of the partial-column paths: o[r] ^= tbl[r] * v for every
+// row, v's selectors given; tbj = the source cell's table words (mm_tbl::cell).
+template <int RM>
+__device__ __forceinline__ void gf_fold_sel(const u32x4 *tbj, int rows, uint32_t s0, uint32_t s1, uint32_t s2,
+					    uint32_t *o)
+{
+#pragma unroll
+	for (int r = 0; r < RM; r++) {
+		if (r < rows) {
+			const u32x4 t = mm_tbl<RM>::row(tbj, 0, r);
+			const uint32_t t2 = mm_tbl<RM>::t2(tbj, 0, r);
+			o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^ __builtin_amdgcn_perm(t[3], t[2], s1) ^
+				__builtin_amdgcn_perm(t2, t2, s2);
+		}
+	}
+}
+
+// v = 4 source bytes
+template <int RM>
+__device__ __forceinline__ void gf_fold_dword(const u32x4 *tbj, int rows, uint32_t v, uint32_t *o)
+{
+	gf_fold_sel<RM>(tbj, rows, v & 0x07070707u, (v >> 3) & 0x07070707u, (v >> 6) & 0x03030303u, o);
+}
+
+// v = one source byte (< 256); the product in the low byte of o[r]
+template <int RM>
+__device__ __forceinline__ void gf_fold_byte(const u32x4 *tbj, int rows, uint32_t v, uint32_t *o)
+{
+	gf_fold_sel<RM>(tbj, rows, v & 7u, (v >> 3) & 7u, v >> 6, o);
+}
+
 // One (stripe, 4 KiB column) item of the product.  Addresses are a
 // wave-uniform 64-bit base per cell (SGPRs) plus the lane's 32-bit offset.
 // The uniform cell offsets are passed through an empty asm per item so LICM
@@ -265,8 +342,7 @@ __device__ __forceinline__ void mm_compute(const ecg_mm_params_t &P, const u32x4
 					   uint32_t s, uint64_t cbase, uint32_t lo, u32x4 *x, u32x4 *keep,
 					   const uint64_t *pa = nullptr)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
+	using TB = mm_tbl<RM>;
 	const int64_t s_dst = (int64_t)s * P.dst_stripe_stride + (int64_t)cbase;
 
 	u32x4 acc[RM];
@@ -315,14 +391,14 @@ __device__ __forceinline__ void mm_compute(const ecg_mm_params_t &P, const u32x4
 				sel1[w] = (v >> 3) & 0x07070707u;
 				sel2[w] = (v >> 6) & 0x03030303u;
 			}
-			u32x4 t2v[T2V];
+			u32x4 t2v[TB::T2V];
 #pragma unroll
-			for (int q = 0; q < T2V; q++)
-				t2v[q] = tb[j * PER_J + RM + q];
+			for (int q = 0; q < TB::T2V; q++)
+				t2v[q] = TB::t2w(tb, j, q);
 #pragma unroll
 			for (int r = 0; r < RM; r++) {
 				if (r < rows) {
-					const u32x4 t = tb[j * PER_J + r];
+					const u32x4 t = TB::row(tb, j, r);
 					const uint32_t t2 = t2v[r / 4][r % 4];
 #pragma unroll
 					for (int w = 0; w < 4; w++) {
@@ -388,13 +464,12 @@ __device__ __forceinline__ void mm_ptr_item(const ecg_mm_params_t &P, const u32x
 
 // The fold of the delta updates (ecg_ptr_kernels.hip ecg_upd_ptr_kernel,
 // ecg_update_masks_kernels.hip): acc[r] ^= tbl[r] * x for the 4 dwords of x
-// (one cell's old ^ new); tb = the column's PER_J = RM + (RM + 3) / 4 table
-// words in the product's LDS layout.
+// (one cell's old ^ new); tb = the column's table words (mm_tbl::cell).
 template <int RM>
 __device__ __forceinline__ void upd_fold(const u32x4 *tb, int rows, const u32x4 x, u32x4 *acc)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	u32x4 sel0, sel1, sel2, t2v[T2V];
+	using TB = mm_tbl<RM>;
+	u32x4 sel0, sel1, sel2, t2v[TB::T2V];
 
 #pragma unroll
 	for (int w = 0; w < 4; w++) {
@@ -403,12 +478,12 @@ __device__ __forceinline__ void upd_fold(const u32x4 *tb, int rows, const u32x4 
 		sel2[w] = (x[w] >> 6) & 0x03030303u;
 	}
 #pragma unroll
-	for (int q = 0; q < T2V; q++)
-		t2v[q] = tb[RM + q];
+	for (int q = 0; q < TB::T2V; q++)
+		t2v[q] = TB::t2w(tb, 0, q);
 #pragma unroll
 	for (int r = 0; r < RM; r++) {
 		if (r < rows) {
-			const u32x4 t = tb[r];
+			const u32x4 t = TB::row(tb, 0, r);
 			const uint32_t t2 = t2v[r / 4][r % 4];
 #pragma unroll
 			for (int w = 0; w < 4; w++)
@@ -430,8 +505,6 @@ template <int KM, int RM, bool ACC, bool DIFF>
 __device__ __forceinline__ void mm_dword(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
 					 uint32_t s, uint64_t off)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
 	constexpr int JB = KM < 4 ? KM : 4;	// loads in flight (more cost k = 16 a wave per SIMD)
 	const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride + off;
 	const uint8_t *sb2 = DIFF ? P.src2 + (int64_t)s * P.src2_stripe_stride + off : nullptr;
@@ -464,19 +537,8 @@ __device__ __forceinline__ void mm_dword(const ecg_mm_params_t &P, const u32x4 *
 		for (int i = 0; i < JB; i++) {
 			const int j = j0 + i;
 
-			if (j >= k)
-				continue;
-			const uint32_t v = x[i];
-			const uint32_t s0 = v & 0x07070707u, s1 = (v >> 3) & 0x07070707u, s2 = (v >> 6) & 0x03030303u;
-#pragma unroll
-			for (int r = 0; r < RM; r++) {
-				if (r < rows) {
-					const u32x4 t = tb[j * PER_J + r];
-					const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r];
-					o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^ __builtin_amdgcn_perm(t[3], t[2], s1) ^
-						__builtin_amdgcn_perm(t2, t2, s2);
-				}
-			}
+			if (j < k)
+				gf_fold_dword<RM>(mm_tbl<RM>::cell(tb, j), rows, x[i], o);
 		}
 	}
 #pragma unroll
@@ -496,8 +558,6 @@ template <int RM, bool ACC, bool DIFF>
 __device__ __forceinline__ void mm_dword_plain(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
 					 uint32_t s, uint64_t off)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
 	const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride + off;
 	const uint8_t *sb2 = DIFF ? P.src2 + (int64_t)s * P.src2_stripe_stride + off : nullptr;
 	uint8_t *db = P.dst + (int64_t)s * P.dst_stripe_stride + off;
@@ -510,16 +570,7 @@ __device__ __forceinline__ void mm_dword_plain(const ecg_mm_params_t &P, const u
 		uint32_t v = *reinterpret_cast<const uint32_t *>(sb + P.src_cell_off[j]);
 		if (DIFF)
 			v ^= *reinterpret_cast<const uint32_t *>(sb2 + P.src2_cell_off[j]);
-		const uint32_t s0 = v & 0x07070707u, s1 = (v >> 3) & 0x07070707u, s2 = (v >> 6) & 0x03030303u;
-#pragma unroll
-		for (int r = 0; r < RM; r++) {
-			if (r < rows) {
-				const u32x4 t = tb[j * PER_J + r];
-				const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r];
-				o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^ __builtin_amdgcn_perm(t[3], t[2], s1) ^
-					__builtin_amdgcn_perm(t2, t2, s2);
-			}
-		}
+		gf_fold_dword<RM>(mm_tbl<RM>::cell(tb, j), rows, v, o);
 	}
 #pragma unroll
 	for (int r = 0; r < RM; r++) {
@@ -538,8 +589,6 @@ template <int RM, bool ACC, bool DIFF>
 __device__ __forceinline__ void mm_tail(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
 				     uint32_t s, uint64_t off, int nb)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
 	const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride;
 	const uint8_t *sb2 = DIFF ? P.src2 + (int64_t)s * P.src2_stripe_stride : nullptr;
 	uint8_t *db = P.dst + (int64_t)s * P.dst_stripe_stride;
@@ -553,17 +602,7 @@ __device__ __forceinline__ void mm_tail(const ecg_mm_params_t &P, const u32x4 *t
 			uint32_t v = sb[P.src_cell_off[j] + off + b];
 			if (DIFF)
 				v ^= sb2[P.src2_cell_off[j] + off + b];
-			const uint32_t s0 = v & 7u, s1 = (v >> 3) & 7u, s2 = v >> 6;
-#pragma unroll
-			for (int r = 0; r < RM; r++) {
-				if (r < rows) {
-					const u32x4 t = tb[j * PER_J + r];
-					const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r];
-					o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^
-						__builtin_amdgcn_perm(t[3], t[2], s1) ^
-						__builtin_amdgcn_perm(t2, t2, s2);
-				}
-			}
+			gf_fold_byte<RM>(mm_tbl<RM>::cell(tb, j), rows, v, o);
 		}
 #pragma unroll
 		for (int r = 0; r < RM; r++) {
@@ -581,8 +620,6 @@ template <int KM, int RM, bool ACC, bool DIFF>
 __device__ __forceinline__ void mm_tail_b(const ecg_mm_params_t &P, const u32x4 *tb, int k, int rows,
 				     uint32_t s, uint64_t off, int nb)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
 	constexpr int JB = KM < 4 ? KM : 4;
 	const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride;
 	const uint8_t *sb2 = DIFF ? P.src2 + (int64_t)s * P.src2_stripe_stride : nullptr;
@@ -614,20 +651,8 @@ __device__ __forceinline__ void mm_tail_b(const ecg_mm_params_t &P, const u32x4 
 			for (int i = 0; i < JB; i++) {
 				const int j = j0 + i;
 
-				if (j >= k)
-					continue;
-				const uint32_t v = x[i];
-				const uint32_t s0 = v & 7u, s1 = (v >> 3) & 7u, s2 = v >> 6;
-#pragma unroll
-				for (int r = 0; r < RM; r++) {
-					if (r < rows) {
-						const u32x4 t = tb[j * PER_J + r];
-						const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r];
-						o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^
-							__builtin_amdgcn_perm(t[3], t[2], s1) ^
-							__builtin_amdgcn_perm(t2, t2, s2);
-					}
-				}
+				if (j < k)
+					gf_fold_byte<RM>(mm_tbl<RM>::cell(tb, j), rows, x[i], o);
 			}
 		}
 #pragma unroll
@@ -734,13 +759,32 @@ __host__ static inline uint32_t mm_wg_cap(const ecg_mm_params_t *p, const ecg_la
 	return c < 2 ? 2 : c;
 }
 
+// The product kernels' 2D grid: x over the 4 KiB columns of a cell, y over
+// the stripes, one item per block; a dimension past 65535 is clamped (the
+// kernels' loops stride) and cfg's grid_x / grid_y (cfg may be NULL) override.
+__host__ static inline void mm_grid(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, uint32_t *gx, uint32_t *gy)
+{
+	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+
+	*gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < 65535 ? nchunk : 65535);
+	*gy = cfg && cfg->grid_y ? cfg->grid_y : (p->nstripes < 65535 ? p->nstripes : 65535);
+}
+
+// The byte kernels' 1D grid: blocks of BLOCK bytes, at most 8192 (they stride).
+__host__ static inline uint32_t mm_byte_grid(const ecg_mm_params_t *p)
+{
+	const uint64_t blocks = (p->cell_bytes * p->nstripes + BLOCK - 1) / BLOCK;
+
+	return (uint32_t)(blocks < 8192 ? blocks : 8192);
+}
+
 // Unused dynamic LDS that leaves room for exactly `cap` blocks per CU (160 KiB
 // of LDS; a block may take at most 64 KiB, so cap >= 2); k, r: the
 // instantiation's (0 = runtime-shaped), whose static table takes the rest.
 __host__ static inline size_t mm_dyn_lds(uint32_t cap, int k, int r)
 {
 	const int km = k ? k : ECG_KMAX_K, rm = r ? r : ECG_KMAX_R;
-	const size_t stat = (size_t)km * (rm + (rm + 3) / 4) * 16;	// ecg_mm_kernel's s_tbl
+	const size_t stat = (size_t)ECG_TBL_WORDS(km, rm) * 16;	// the kernel's s_tbl
 	size_t d;
 
 	if (cap == 0)

@@ -32,8 +32,6 @@ template <int KM, int RM>
 __device__ __forceinline__ void mm_ptr_bytes(const u32x4 *tb, int k, int rows, const uint64_t *pt, uint64_t off,
 					     int nb)
 {
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
 	constexpr int JB = KM < 4 ? KM : 4;
 	const bool dw = nb == 4;
 
@@ -57,19 +55,9 @@ __device__ __forceinline__ void mm_ptr_bytes(const u32x4 *tb, int k, int rows, c
 			for (int i = 0; i < JB; i++) {
 				const int j = j0 + i;
 
-				if (j >= k)
-					continue;
-				const uint32_t v = x[i];
-				const uint32_t s0 = v & 0x07070707u, s1 = (v >> 3) & 0x07070707u, s2 = (v >> 6) & 0x03030303u;
-#pragma unroll
-				for (int r = 0; r < RM; r++) {
-					if (r < rows) {
-						const u32x4 t = tb[j * PER_J + r];
-						const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r];
-						o[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^
-							__builtin_amdgcn_perm(t[3], t[2], s1) ^ __builtin_amdgcn_perm(t2, t2, s2);
-					}
-				}
+				// a byte folds as the dword whose upper bytes are zero
+				if (j < k)
+					gf_fold_dword<RM>(mm_tbl<RM>::cell(tb, j), rows, x[i], o);
 			}
 		}
 #pragma unroll
@@ -91,24 +79,14 @@ ecg_mm_ptr_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
-	__shared__ u32x4 s_tbl[KM * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, RM)];
 	const int k = K ? K : (int)P.k;
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<G>();
 
-	for (int i = threadIdx.x; i < KM * RM; i += BLOCK) {
-		const int j = i / RM, r = i % RM;
-		if (j < k && r < rows) {
-			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
-		}
-	}
-	__syncthreads();
+	tbl_stage<RM>(s_tbl, P, KM, k, rows);
 
 	for (uint32_t s = blockIdx.y; s < P.nstripes; s += gridDim.y) {
 		const uint64_t *pt = cells + (uint64_t)s * (uint32_t)(k + rows);
@@ -204,7 +182,7 @@ template <int RM, int G>
 __device__ __forceinline__ void upd_col(const u32x4 *s_tbl, const uint64_t *it, int rows, uint32_t n,
 					uint64_t cols, uint32_t ncols, uint64_t off)
 {
-	constexpr int PER_J = RM + (RM + 3) / 4;
+	using TB = mm_tbl<RM>;
 	u32x4 acc[RM];
 
 #pragma unroll
@@ -222,11 +200,11 @@ __device__ __forceinline__ void upd_col(const u32x4 *s_tbl, const uint64_t *it, 
 			     ld_g<G>(reinterpret_cast<const uint8_t *>(pr[3]) + off);
 		const uint32_t j0 = (uint32_t)(cols >> (8 * m)) & 0xffu;
 		if (j0 < ncols)
-			upd_fold<RM>(s_tbl + j0 * PER_J, rows, x0, acc);
+			upd_fold<RM>(TB::cell(s_tbl, j0), rows, x0, acc);
 		if (two) {
 			const uint32_t j1 = (uint32_t)(cols >> (8 * (m + 1))) & 0xffu;
 			if (j1 < ncols)
-				upd_fold<RM>(s_tbl + j1 * PER_J, rows, x1, acc);
+				upd_fold<RM>(TB::cell(s_tbl, j1), rows, x1, acc);
 		}
 	}
 #pragma unroll
@@ -241,7 +219,6 @@ template <int RM>
 __device__ __forceinline__ void upd_dword(const u32x4 *s_tbl, const uint64_t *it, int rows, uint32_t n,
 					  uint64_t cols, uint32_t ncols, uint64_t off)
 {
-	constexpr int PER_J = RM + (RM + 3) / 4;
 	uint32_t a[RM];
 
 #pragma unroll
@@ -253,20 +230,9 @@ __device__ __forceinline__ void upd_dword(const u32x4 *s_tbl, const uint64_t *it
 		const uint32_t j = (uint32_t)(cols >> (8 * m)) & 0xffu;
 		const uint32_t v = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(pr[0]) + off) ^
 				   *reinterpret_cast<const uint32_t *>(reinterpret_cast<const uint8_t *>(pr[1]) + off);
-		const uint32_t s0 = v & 0x07070707u, s1 = (v >> 3) & 0x07070707u, s2 = (v >> 6) & 0x03030303u;
 
-		if (j >= ncols)
-			continue;
-		const u32x4 *tb = s_tbl + j * PER_J;
-#pragma unroll
-		for (int r = 0; r < RM; r++) {
-			if (r < rows) {
-				const u32x4 t = tb[r];
-				const uint32_t t2 = reinterpret_cast<const uint32_t *>(&tb[RM])[r];
-				a[r] ^= __builtin_amdgcn_perm(t[1], t[0], s0) ^ __builtin_amdgcn_perm(t[3], t[2], s1) ^
-					__builtin_amdgcn_perm(t2, t2, s2);
-			}
-		}
+		if (j < ncols)
+			gf_fold_dword<RM>(mm_tbl<RM>::cell(s_tbl, j), rows, v, a);
 	}
 #pragma unroll
 	for (int r = 0; r < RM; r++)
@@ -279,20 +245,21 @@ __global__ void __launch_bounds__(BLOCK)
 ecg_upd_ptr_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ items, uint32_t ncols)
 {
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int PER_J = RM + (RM + 3) / 4;
-	__shared__ u32x4 s_tbl[ECG_KMAX_K * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, RM)];
 	const int rows = R ? R : (int)P.rows;
 	const uint32_t rec = (uint32_t)ECG_UPD_REC(rows);
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<G>();
 
+	// tbl_stage's loop, written out: called here, it changed how the columns of
+	// the runtime-shaped instantiations (upd_col, R = 0) are scheduled
 	for (int i = threadIdx.x; i < ECG_KMAX_K * RM; i += BLOCK) {
 		const int j = i / RM, r = i % RM;
 		if (j < (int)ncols && r < rows) {
 			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
+			s_tbl[ECG_TBL_ROW(RM, j, r)] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
+			reinterpret_cast<uint32_t *>(&s_tbl[ECG_TBL_ROW(RM, j, RM)])[r] = t.t2;
 		}
 	}
 	__syncthreads();
@@ -379,8 +346,7 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 {
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t C = p->cell_bytes;
-	const uint64_t nchunk = (C + CHUNK_BYTES - 1) / CHUNK_BYTES;
-	uint32_t id = N_UKERNELS;
+	uint32_t id = N_UKERNELS, gx, gy;
 
 	if (p->nstripes == 0 || C == 0)
 		return (int)hipSuccess;
@@ -389,10 +355,7 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 	if ((granule == 16 && (C & 15u)) || (granule == 4 && (C & 3u)))
 		granule = 0;
 	if (granule == 0) {
-		uint64_t blocks = (C * p->nstripes + BLOCK - 1) / BLOCK;
-		if (blocks > 8192)
-			blocks = 8192;
-		hipLaunchKernelGGL(ecg_upd_ptr_byte_kernel, dim3((uint32_t)blocks), dim3(BLOCK), 0, st, *p, items_dev,
+		hipLaunchKernelGGL(ecg_upd_ptr_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p, items_dev,
 				   ncols);
 		if (kernel_id)
 			*kernel_id = KID_UPD_BYTE;
@@ -403,8 +366,7 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 	for (uint32_t i = 0; i < N_UKERNELS && id == N_UKERNELS; i++)
 		if (g_ukernels[i].g == granule && (g_ukernels[i].r == (int)p->rows || g_ukernels[i].r == 0))
 			id = i;
-	const uint32_t gx = (uint32_t)(nchunk < 65535 ? nchunk : 65535);
-	const uint32_t gy = p->nstripes < 65535 ? p->nstripes : 65535;
+	mm_grid(p, nullptr, &gx, &gy);
 	hipLaunchKernelGGL(g_ukernels[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, items_dev, ncols);
 	if (kernel_id)
 		*kernel_id = KID_UPD + id;
@@ -452,9 +414,8 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 				       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
 	int g = granule;
-	uint32_t id = N_PKERNELS;
+	uint32_t id = N_PKERNELS, gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
 		return (int)hipSuccess;
@@ -462,11 +423,7 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 		g = 4;
 	if (g == 0 || (cfg && cfg->variant == 2)) {	/* 0: the host found operands the
 							 * device cannot serve as dwords */
-		uint64_t blocks = (p->cell_bytes * p->nstripes + BLOCK - 1) / BLOCK;
-		if (blocks > 8192)
-			blocks = 8192;
-		hipLaunchKernelGGL(ecg_mm_ptr_byte_kernel, dim3((uint32_t)blocks), dim3(BLOCK), 0, st, *p,
-				   cells_dev);
+		hipLaunchKernelGGL(ecg_mm_ptr_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p, cells_dev);
 		if (kernel_id)
 			*kernel_id = KID_PTR_BYTE;
 		return (int)hipGetLastError();
@@ -488,8 +445,7 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 			id = i;
 	if (id == N_PKERNELS)
 		return (int)hipErrorInvalidDeviceFunction;
-	uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < 65535 ? nchunk : 65535);
-	uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (p->nstripes < 65535 ? p->nstripes : 65535);
+	mm_grid(p, cfg, &gx, &gy);
 	// blocks per CU as the offset kernel's (ecg_set_wg_per_cu): unused dynamic LDS
 	const size_t lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_pkernels[id].k, g_pkernels[id].r);
 	hipLaunchKernelGGL(g_pkernels[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev);

@@ -118,14 +118,13 @@ struct rm_table {
 // output rows at most (a stripe's e <= p rows run with rows = e).  16-byte
 // lanes only: every cell address 16-byte aligned and C % 16 == 0 (the
 // launcher sends everything else to the byte kernel), so a partial last column
-// is a lane mask.  s_tbl: the block's KM * (RM + 1) staged table words.
+// is a lane mask.  s_tbl: the block's ECG_TBL_WORDS(KM, RM) staged table words.
 template <int K, int RM, class Addr>
 __device__ __forceinline__ void rm_lanes(const ecg_mm_params_t &P, u32x4 *s_tbl, const u32x4 *__restrict__ settbl,
 					 const uint32_t *__restrict__ masks, unsigned long long *result,
 					 uint32_t grp, uint32_t nsets, Addr A)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
-	constexpr int PER_J = RM + 1;	// RM + T2V, RM <= 4
 	const int k = K ? K : (int)P.k;
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
@@ -145,7 +144,7 @@ __device__ __forceinline__ void rm_lanes(const ecg_mm_params_t &P, u32x4 *s_tbl,
 
 			if (staged != idx) {
 				__syncthreads();	// the previous stripe's columns are done with s_tbl
-				if ((int)threadIdx.x < k * PER_J)
+				if ((int)threadIdx.x < ECG_TBL_WORDS(k, RM))
 					s_tbl[threadIdx.x] = ent[2 + threadIdx.x];
 				__syncthreads();
 				staged = idx;
@@ -206,7 +205,6 @@ __device__ __forceinline__ void rm_bytes(const ecg_mm_params_t &P, const u32x4 *
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const int k = (int)P.k, p = (int)P.rows;
-	const int per_j = p + 1;
 	const uint32_t entq = ECG_RM_ENT_Q(k, p);
 	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
 	const rm_read read = {masks, k, p, nsets, settbl, entq};
@@ -231,12 +229,13 @@ __device__ __forceinline__ void rm_bytes(const ecg_mm_params_t &P, const u32x4 *
 
 					for (int j = 0; j < k; j++) {
 						const uint32_t x = *A.byte(dec[j], i);
-						const u32x4 t2 = ent[2 + j * per_j + p];
+						// the set's tables: p <= 3 rows, one t2 word
+						const u32x4 t2 = ent[2 + ECG_TBL_ROW(p, j, p)];
 
 #pragma unroll
 						for (int r = 0; r < ECG_RM_MAX_P; r++) {
 							if (r < e) {
-								const u32x4 t = ent[2 + j * per_j + r];
+								const u32x4 t = ent[2 + ECG_TBL_ROW(p, j, r)];
 								const ecg_ptbl_t pt = {t[0], t[1], t[2], t[3], t2[r]};
 
 								o[r] ^= gf_mul1(pt, x);
@@ -263,7 +262,7 @@ ecg_recover_masks_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ sett
 			 const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp,
 			 uint32_t nsets)
 {
-	__shared__ u32x4 s_tbl[(K ? K : ECG_KMAX_K) * (RM + 1)];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(K ? K : ECG_KMAX_K, RM)];
 
 	rm_lanes<K, RM>(P, s_tbl, settbl, masks, result, grp, nsets,
 			rm_strided(P.src, P.src_stripe_stride, P.cell_bytes));
@@ -283,7 +282,7 @@ ecg_recover_masks_ptr_kernel(const ecg_mm_params_t P, const u32x4 *__restrict__ 
 			     const uint64_t *__restrict__ cells, const uint32_t *__restrict__ masks,
 			     unsigned long long *result, uint32_t grp, uint32_t nsets)
 {
-	__shared__ u32x4 s_tbl[(K ? K : ECG_KMAX_K) * (RM + 1)];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(K ? K : ECG_KMAX_K, RM)];
 
 	rm_lanes<K, RM>(P, s_tbl, settbl, masks, result, grp, nsets,
 			rm_table(cells, (uint32_t)((K ? K : (int)P.k) + RM)));

@@ -65,8 +65,7 @@ ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl
 		  const uint32_t *__restrict__ status, unsigned long long *result)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
-	constexpr int PER_J = 2;	// RM + T2V of one output row
-	__shared__ u32x4 s_tbl[KM * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, 1)];	// one output row
 	const int k = K ? K : (int)P.k;
 	const int p = (int)P.rows;
 	const uint64_t C = P.cell_bytes;
@@ -86,10 +85,12 @@ ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl
 			if (staged != c) {
 				__syncthreads();	// the previous stripe's columns are done with s_tbl
 				if ((int)threadIdx.x < k) {
+					// written out, the whole t2 word: with mm_tbl<1>::put here
+					// the columns of K = 4, 8, 16 were scheduled differently
 					const ecg_ptbl_t t = rowtbl[c * k + (int)threadIdx.x];
 
-					s_tbl[threadIdx.x * PER_J] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-					s_tbl[threadIdx.x * PER_J + 1] = (u32x4){t.t2, 0u, 0u, 0u};
+					s_tbl[ECG_TBL_ROW(1, threadIdx.x, 0)] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
+					s_tbl[ECG_TBL_ROW(1, threadIdx.x, 1)] = (u32x4){t.t2, 0u, 0u, 0u};
 				}
 				__syncthreads();
 				staged = c;

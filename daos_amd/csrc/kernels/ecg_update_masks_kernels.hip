@@ -10,8 +10,8 @@
 // reads a stripe's mask word with the one reading the host shares (ecg_kabi.h
 // ecg_update_mask_read), and a ballot leaves the stripes with work as a
 // wave-uniform 64-bit mask.  The perm tables of all k columns x p rows do not
-// depend on the stripe: they are staged into LDS once per block, in
-// ecg_upd_ptr_kernel's layout (PER_J = RM + (RM + 3) / 4 words).  Per 4 KiB
+// depend on the stripe: they are staged into LDS once per block (ecg_mm_dev.h
+// tbl_stage; the layout: ecg_kabi.h ECG_TBL_PER_J).  Per 4 KiB
 // column a lane loads its 16 bytes of every parity row first, then walks the
 // mask's set bits two at a time -- four cell loads in flight -- folding each
 // delta into the rows (ecg_mm_dev.h upd_fold), and stores each parity row
@@ -73,8 +73,8 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 			uint32_t grp, uint32_t packed)
 {
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int PER_J = RM + (RM + 3) / 4;
-	__shared__ u32x4 s_tbl[ECG_KMAX_K * PER_J];
+	using TB = mm_tbl<RM>;
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, RM)];
 	const int k = (int)P.k;
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
@@ -83,15 +83,7 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
 	const um_read read = {masks, k};
 
-	for (int i = threadIdx.x; i < ECG_KMAX_K * RM; i += BLOCK) {
-		const int j = i / RM, r = i % RM;
-		if (j < k && r < rows) {
-			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
-		}
-	}
-	__syncthreads();
+	tbl_stage<RM>(s_tbl, P, ECG_KMAX_K, k, rows);
 
 	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
 		uint32_t mw, m;
@@ -129,9 +121,11 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 						const uint64_t c1 = um_cell(packed, i + 1u, j1, C) + off;
 						x1 = ld_g<16>(ob + c1) ^ ld_g<16>(nb + c1);
 					}
-					upd_fold<RM>(s_tbl + j0 * PER_J, rows, x0, acc);
+					// (the unsigned bit index times PER_J, not TB::cell's int:
+					// that one folds into another scalar sequence)
+					upd_fold<RM>(s_tbl + j0 * TB::PER_J, rows, x0, acc);
 					if (two)
-						upd_fold<RM>(s_tbl + j1 * PER_J, rows, x1, acc);
+						upd_fold<RM>(s_tbl + j1 * TB::PER_J, rows, x1, acc);
 				}
 #pragma unroll
 				for (int r = 0; r < RM; r++)

@@ -28,17 +28,8 @@
 
 namespace {
 
-// c * v for the 4 bytes of v, table read back from the block's LDS copy
-// (s_tbl layout of ecg_mm_kernel: cell-major, RM x 16 B then the t2 words)
-template <int RM>
-__device__ __forceinline__ ecg_ptbl_t tbl_of(const u32x4 *tb, int j, int r)
-{
-	constexpr int PER_J = RM + (RM + 3) / 4;
-	const u32x4 t = tb[j * PER_J + r];
-
-	return (ecg_ptbl_t){t[0], t[1], t[2], t[3], reinterpret_cast<const uint32_t *>(&tb[j * PER_J + RM])[r]};
-}
-
+// c * v for the 4 bytes of v (the tables are read back from the block's LDS
+// copy: ecg_mm_dev.h mm_tbl::entry)
 __device__ __forceinline__ uint32_t gf_mul4v(const ecg_ptbl_t &t, uint32_t v)
 {
 	return gf_mul4(t, v & 0x07070707u, (v >> 3) & 0x07070707u, (v >> 6) & 0x03030303u);
@@ -59,13 +50,13 @@ __device__ __forceinline__ void verify_dirty(const u32x4 *tb, int k, int rows, c
 	if (rows >= 2) {
 #pragma nounroll
 		for (int j = 0; j < k; j++) {
-			const ecg_ptbl_t t0 = tbl_of<RM>(tb, j, 0);
+			const ecg_ptbl_t t0 = mm_tbl<RM>::entry(tb, j, 0);
 			uint32_t bad = 0;
 
 #pragma unroll
 			for (int r = 1; r < RM; r++) {
 				if (r < rows) {
-					const ecg_ptbl_t tr = tbl_of<RM>(tb, j, r);
+					const ecg_ptbl_t tr = mm_tbl<RM>::entry(tb, j, r);
 #pragma unroll
 					for (int w = 0; w < 4; w++)
 						bad |= gf_mul4v(t0, syn[r][w]) ^ gf_mul4v(tr, syn[0][w]);
@@ -107,24 +98,14 @@ ecg_verify_kernel(const ecg_mm_params_t P, uint32_t *__restrict__ status)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
 	constexpr int RM = R ? R : ECG_KMAX_R;
-	constexpr int T2V = (RM + 3) / 4;
-	constexpr int PER_J = RM + T2V;
-	__shared__ u32x4 s_tbl[KM * PER_J];
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, RM)];
 	const int k = K ? K : (int)P.k;
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
 	const uint32_t lo = lane_off<16>();
 
-	for (int i = threadIdx.x; i < KM * RM; i += BLOCK) {
-		const int j = i / RM, r = i % RM;
-		if (j < k && r < rows) {
-			const ecg_ptbl_t &t = P.tbl[r][j];
-			s_tbl[j * PER_J + r] = (u32x4){t.t0lo, t.t0hi, t.t1lo, t.t1hi};
-			reinterpret_cast<uint32_t *>(&s_tbl[j * PER_J + RM])[r] = t.t2;
-		}
-	}
-	__syncthreads();
+	tbl_stage<RM>(s_tbl, P, KM, k, rows);
 
 	// one item per block; the loops only stride when a grid dimension would
 	// exceed 65535
@@ -304,14 +285,13 @@ extern "C" int ecg_k_launch_verify(const ecg_mm_params_t *p, uint32_t *status, i
 				   const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	const uint64_t nchunk = (p->cell_bytes + CHUNK_BYTES - 1) / CHUNK_BYTES;
+	uint32_t gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
 		return (int)hipSuccess;
 	if (p->k == 0 || p->k > ECG_KMAX_K || p->rows > ECG_KMAX_R || status == nullptr)
 		return (int)hipErrorInvalidValue;
-	const uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)(nchunk < 65535 ? nchunk : 65535);
-	const uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (p->nstripes < 65535 ? p->nstripes : 65535);
+	mm_grid(p, cfg, &gx, &gy);
 
 	if (bytewise) {
 		hipLaunchKernelGGL(ecg_verify_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, status);

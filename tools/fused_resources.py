@@ -36,6 +36,11 @@ report`).  Needs no GPU.
       ecg_update_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
       exit 1 if one uses scratch.  NEW BASE pairs as for --repair (upd_fold
       moved into ecg_mm_dev.h)
+  python tools/fused_resources.py --kept NEW.txt BASE.txt [NEW.txt BASE.txt]...
+      a refactor's check over any kernel files: every kernel of each BASE
+      found by name in its NEW with VGPRs, AGPRs, scratch and LDS equal or
+      lower and occupancy not lower (exit 1 otherwise); kernels whose
+      figures differ at all are listed
 
 The SRC flag is the last template argument of ecg_mm_csum_kernel; a build
 from before it existed mangles the plain instantiations without it, which
@@ -164,6 +169,28 @@ def kept_identical(new_txt, base_txt):
     return int(bool(diff))
 
 
+def kept_or_lower(*pairs):
+    """Every kernel of each BASE remarks file found by name in its NEW file with VGPRs, AGPRs,
+    scratch and LDS equal or lower and occupancy equal or higher; the kernels whose figures
+    (SGPRs included) differ at all are listed."""
+    bad = total = 0
+    for new_txt, base_txt in zip(pairs[0::2], pairs[1::2]):
+        new, base = parse_named(new_txt, ANY), parse_named(base_txt, ANY)
+        total += len(base)
+        for key in sorted(base):
+            b, n = base[key], new.get(key)
+            if n == b:
+                continue
+            worse = n is None or n["Occupancy [waves/SIMD]"] < b["Occupancy [waves/SIMD]"] or any(
+                n[f] > b[f] for f in ("VGPRs", "AGPRs", "ScratchSize [bytes/lane]", "LDS Size [bytes/block]"))
+            what = "MISSING" if n is None else ", ".join(f"{f} {b[f]} -> {n[f]}" for f in FIELDS if n[f] != b[f])
+            print(f"| `{key[0]}` | {what} | {'WORSE' if worse else 'ok'} |")
+            bad |= worse
+    print(f"\n{total} kernels of the base compared: " + ("A KERNEL IS WORSE OR MISSING" if bad else
+          "VGPRs, AGPRs, scratch and LDS equal or lower and occupancy not lower in every one"))
+    return int(bad)
+
+
 MASKED = re.compile(r"ecg_(crc|adler)_masked_kernelI(?:Li(\d+)ELb([01])E)?Lb([01])E")
 
 
@@ -196,6 +223,8 @@ def csum_masked_table(new_txt, base_txt):
 
 
 def main():
+    if sys.argv[1] == "--kept":
+        return kept_or_lower(*sys.argv[2:])
     if sys.argv[1] == "--csum-masked":
         return csum_masked_table(*sys.argv[2:4])
     if sys.argv[1] == "--verify":
