@@ -24,8 +24,8 @@ static const struct crc_def g_defs[4] = {
 	[ECG_HASH_CRC64] = {64, 1, 0xC96C5795D7870F42ull, ~0ull, ~0ull},
 };
 
-/* CRC table kinds are fixed per kernel (ecg_kernels.hip CS_TB,
- * ecg_csum_kernels.hip kind_ok): standalone kernels use the nibble tables
+/* CRC table kinds are fixed per kernel (ecg_kernels.hip CS_TB, the tables of
+ * ecg_csum_kernels.hip): standalone kernels use the nibble tables
  * (SDWA-addressed, conflict-free; profiles/r03/crc_sq/), their byte-granular
  * variants the 5-bit tables; the fused kernels the byte tables for crc64 and
  * for crc32 at EC_8P2, the 5-bit tables elsewhere (profiles/r02/fused_tables_ab/,
@@ -206,22 +206,30 @@ static uint64_t crc_raw(const struct crc_def *d, const unsigned char *buf, int l
 	return c;
 }
 
-/* 5-bit field tables (ecg_kabi.h p5 / a5): field (dword j, field i) covers
- * bits 32j + 5i .. +4 of the piece or register; entry v = XOR of the basis
- * images of v's set bits.  a5 for a shift of n zero bytes. */
-static void build_p5(const struct crc_def *d, uint64_t zeros, uint64_t *p5)
+/* basis[k]: the raw CRC of the 16-byte piece whose only set bit is bit k,
+ * followed by `zeros` zero bytes -- what the p5 and q4 tables are XORs of */
+static void piece_basis(const struct crc_def *d, uint64_t zeros, uint64_t basis[128])
 {
 	const uint64_t sh = zeros ? crc_xpow8(d, zeros) : 0;
-	uint64_t basis[128];
 	unsigned char piece[16];
 
 	for (int k = 0; k < 128; k++) {
 		memset(piece, 0, sizeof(piece));
 		piece[k / 8] = (unsigned char)(1u << (k % 8));
 		basis[k] = crc_raw(d, piece, 16);
-		if (zeros)	/* the piece followed by `zeros` zero bytes */
+		if (zeros)
 			basis[k] = crc_mulmod(d, basis[k], sh);
 	}
+}
+
+/* 5-bit field tables (ecg_kabi.h p5 / a5): field (dword j, field i) covers
+ * bits 32j + 5i .. +4 of the piece or register; entry v = XOR of the basis
+ * images of v's set bits.  a5 for a shift of n zero bytes. */
+static void build_p5(const struct crc_def *d, uint64_t zeros, uint64_t *p5)
+{
+	uint64_t basis[128];
+
+	piece_basis(d, zeros, basis);
 	for (int f = 0; f < ECG_CSUM_NF5; f++) {
 		const int j = f / 7, i = f % 7;
 
@@ -241,17 +249,9 @@ static void build_p5(const struct crc_def *d, uint64_t zeros, uint64_t *p5)
  * shifted by n zero bytes (a4) */
 static void build_q4(const struct crc_def *d, uint64_t zeros, uint64_t *q4)
 {
-	const uint64_t sh = zeros ? crc_xpow8(d, zeros) : 0;
 	uint64_t basis[128];
-	unsigned char piece[16];
 
-	for (int k = 0; k < 128; k++) {
-		memset(piece, 0, sizeof(piece));
-		piece[k / 8] = (unsigned char)(1u << (k % 8));
-		basis[k] = crc_raw(d, piece, 16);
-		if (zeros)
-			basis[k] = crc_mulmod(d, basis[k], sh);
-	}
+	piece_basis(d, zeros, basis);
 	for (int t = 0; t < 32; t++)
 		for (int v = 0; v < 16; v++) {
 			uint64_t c = 0;
@@ -663,13 +663,12 @@ int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_
 	} else {
 		prm.variant = 0;	/* adler32: the kernel picks by shape */
 	}
+	ecg_trace_push("ecg:csum_extents");
 	e = ecg_k_launch_csum(&prm, (void *)ecg_pick_stream(ctx, stream), ctx->csum_blocks, &kid);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "csum kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)prm.n_ext * prm.nchunks);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
-	return 0;
+	rc = ecg_launch_done(ctx, e, "csum kernel launch", 1, ecg_k_kernel_name(kid));
+	if (rc == 0)
+		ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)prm.n_ext * prm.nchunks);
+	return rc;
 }
 
 int ecg_set_csum_launch(ecg_ctx_t *ctx, uint32_t max_blocks)
@@ -748,12 +747,9 @@ int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want
 		return ecg_hip_fail(he, "csum_compare memset");
 	if (n == 0)
 		return 0;
+	ecg_trace_push("ecg:csum_compare");
 	e = ecg_k_launch_csum_compare(got, want, n, (uint32_t)cl, result, (void *)st, &kid);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "csum_compare kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "csum_compare kernel launch", 1, ecg_k_kernel_name(kid));
 }
 
 int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
@@ -781,13 +777,10 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 		return rc;
 	if (nstripes == 0 || ncells == 0 || nch == 0)
 		return 0;
+	ecg_trace_push("ecg:csum_mask");
 	e = ecg_k_launch_csum_mask(got, want, nstripes, ncells, nch, stripe_stride, cell_stride, first_cell,
 				   (uint32_t)cl, masks, (void *)ecg_pick_stream(ctx, stream), &kid);
-	if (e != 0)
-		return ecg_hip_fail((hipError_t)e, "csum_mask kernel launch");
-	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
-	return 0;
+	return ecg_launch_done(ctx, e, "csum_mask kernel launch", 1, ecg_k_kernel_name(kid));
 }
 
 /* [a, a + alen) and [b, b + blen) share a byte */
@@ -894,7 +887,6 @@ int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_s
 {
 	struct masked_geom g;
 	hipStream_t st;
-	hipError_t he;
 	int rc;
 
 	rc = masked_check("csum_masked", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride, masks, which,
@@ -908,11 +900,9 @@ int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_s
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 	/* result = {0, UINT64_MAX, 0, 0}, as ecg_recover_masks presets it */
-	he = hipMemsetAsync(result, 0, 32, st);
-	if (he == hipSuccess)
-		he = hipMemsetAsync((uint8_t *)result + 8, 0xFF, 8, st);
-	if (he != hipSuccess)
-		return ecg_hip_fail(he, "csum_masked memset");
+	rc = ecg_result_reset(result, st, "csum_masked memset");
+	if (rc)
+		return rc;
 	if (S == 0 || C == 0)
 		return 0;
 	return masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks, which, csums, result, st);

@@ -24,6 +24,12 @@
 //    bytes of the chunk, the standard identity for reflected CRCs.
 // Tables live in LDS (crc16 4 KiB, crc32 8 KiB, crc64 32 KiB per block) and
 // blocks stride over chunks so each block loads them once.
+//
+// Each kernel family is built from one body.  The wave-per-item kernels of
+// extents and of masked cells are crc_wave / adler_wave over an addressing
+// struct (cs_extents, cs_masked); the group and split kernels keep their own
+// loops and take the CRC prologue and finish (crc_lane) and the adler32 sums
+// (adler_lane, adler_wave_sum, adler_finish) from the same helpers.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -36,10 +42,6 @@ using namespace ecg_crc;
 
 constexpr int CS_BLOCK = 256;
 constexpr int CS_WAVES = CS_BLOCK / 64;
-#ifndef ECG_CS_UNROLL
-#define ECG_CS_UNROLL 4
-#endif
-constexpr int CS_UNROLL = ECG_CS_UNROLL;	// pieces in flight per lane
 constexpr uint32_t ADLER_MOD = 65521;
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
@@ -60,94 +62,102 @@ __device__ __forceinline__ void load16(const uint8_t *p, uint32_t d[4])
 	}
 }
 
-__device__ __forceinline__ void chunk_geom(const ecg_csum_params_t &p, uint64_t g, uint64_t &off,
-					   uint64_t &len, const uint8_t *&base)
+// CRC table kinds (ecg_kabi.h): TK_5 conflict-free 5-bit fields (the
+// byte-granular kernels), TK_4 nibble fields addressed by SDWA byte selects
+// (the aligned kernels: fewest VALU per lookup, and the CRC kernels are
+// VALU-issue bound -- profiles/r03/crc_sq)
+constexpr int TK_5 = 0, TK_4 = 2;
+
+// One Horner step of a lane's accumulator over the ECG_CSUM_P5U pieces d (s5 =
+// positional q then a): acc * x^(8 * P5U * stride) ^ crc(pieces)
+template <int W, int TK, typename T>
+__device__ __forceinline__ T horner(T acc, const uint32_t (*d)[4], const T *s5)
 {
-	const uint64_t e = g / p.nchunks, c = g - e * p.nchunks;
-
-	off = c == 0 ? 0 : p.first_bytes + (c - 1) * p.chunk_bytes;
-	len = c == 0 ? p.first_bytes : p.chunk_bytes;
-	if (off + len > p.ext_bytes)
-		len = p.ext_bytes - off;
-	base = p.src + (int64_t)e * p.ext_stride + off;
-}
-
-// CRC table kinds (ecg_kabi.h): TK_5 conflict-free 5-bit fields, TK_B8 byte
-// tables (the A/B variant), TK_4 nibble fields addressed by SDWA byte selects
-// (the default: fewest VALU per lookup, and the CRC kernels are VALU-issue
-// bound -- profiles/r03/crc_sq)
-constexpr int TK_5 = 0, TK_B8 = 1, TK_4 = 2;
-
-// Horner steps of a lane's accumulator over the UN pieces d[0..UN-1] (those
-// with i + u < m): byte tables (sl, sh), one step per piece, acc * x^(8 *
-// stride) ^ crc(piece); 5-bit / nibble tables (s5 = positional q then a),
-// one step per UN = ECG_CSUM_P5U pieces (m is then a multiple of UN).
-template <int W, bool REFL, int TK, int UN, typename T>
-__device__ __forceinline__ T horner(T acc, const uint32_t (*d)[4], int64_t i, int64_t m, const T *s5,
-				    const T *sl, const T *sh)
-{
-	if constexpr (TK == TK_B8) {
-#pragma unroll
-		for (int u = 0; u < UN; u++)
-			if (i + u < m)
-				acc = lin_map<W>(acc, sh) ^ piece_crc<W, REFL>(d[u], sl);
-		return acc;
-	} else if constexpr (TK == TK_4) {
-		static_assert(UN == ECG_CSUM_P5U, "nibble path steps ECG_CSUM_P5U pieces at a time");
-		return horner4u<W, UN>(acc, d, s5, nib_hmask<T>());
-	} else {
-		static_assert(UN == ECG_CSUM_P5U, "5-bit path steps ECG_CSUM_P5U pieces at a time");
+	if constexpr (TK == TK_4)
+		return horner4u<W, ECG_CSUM_P5U>(acc, d, s5, nib_hmask<T>());
+	else
 		return horner5u<W>(acc, d, s5);
-	}
 }
 
-// LDS images of one kernel: the positional 5-bit or nibble tables (q, a), or
-// the byte tables; UN pieces in flight per lane
+// LDS image of one kernel: the positional 5-bit or nibble tables (q, a); UN
+// pieces in flight per lane
 template <int W, int TK>
 struct crc_lds {
 	using T = typename reg<W>::T;
-	static constexpr int NB = W / 8;
-	static constexpr int N5 = TK == TK_B8 ? 1 : TK == TK_4 ? f4u<W>::N : f5u<W>::N;
-	static constexpr int NSL = TK == TK_B8 ? NB * 256 : 1;
-	static constexpr int UN = TK == TK_B8 ? CS_UNROLL : ECG_CSUM_P5U;
+	static constexpr int N5 = TK == TK_4 ? f4u<W>::N : f5u<W>::N;
+	static constexpr int UN = ECG_CSUM_P5U;
 };
 
 // positional tables of stride `q_off` (5-bit p5x / nibble q4) and the
 // U-stride shift into LDS
 template <int W, int TK, typename T>
-__device__ __forceinline__ void stage_tables(T *s5, T *sl, T *sh, const T *gt, int p5x_off, int a5_off,
-					     int q4_off, int a4_off, int nthreads)
+__device__ __forceinline__ void stage_tables(T *s5, const T *gt, int p5x_off, int a5_off, int q4_off, int a4_off,
+					     int nthreads)
 {
-	constexpr int NB = W / 8;
-	if constexpr (TK == TK_B8) {
-		for (int i = threadIdx.x; i < NB * 256; i += nthreads) {
-			sl[i] = gt[i];
-			sh[i] = gt[NB * 256 + i];
-		}
-	} else if constexpr (TK == TK_4) {
+	if constexpr (TK == TK_4)
 		stage4u<W, ECG_CSUM_P5U>(s5, gt, q4_off, a4_off, nthreads);
-	} else {
-		stage5u<W>(s5, gt, p5x_off, a5_off, nthreads);
-	}
-}
-
-// the lane's final shift x^(8*16*(G-1-l)) (G lanes per chunk; klane = its
-// k64 entry): reflected CRCs from the nibl tables (W/4 steps), else mulmod
-template <int W, bool REFL, typename T>
-__device__ __forceinline__ T lane_shift(T acc, T klane, const T *gt, const T *r4, uint32_t nib_lane, T poly)
-{
-	if constexpr (REFL)
-		return lane_mul_nib<W>(acc, gt + ECG_CSUM_OFF_NIBL(W / 8), r4, nib_lane);
 	else
-		return mulmod<W, REFL>(klane, acc, poly);
+		stage5u<W>(s5, gt, p5x_off, a5_off, nthreads);
 }
 
-// lane steps of a chunk of nq pieces, `per` pieces per step
-template <int TK>
+// What a lane of a CRC kernel keeps beside its tables in LDS, and the two ends
+// of every chunk.  stage(): the kernel's prologue up to (not including) its
+// barrier -- the positional tables of the stride at the four offsets and r4
+// into LDS, the lane's constants into registers; kidx is the lane's column of
+// k64 / nibl: x^(8*16*(63-kidx)) is its final shift.
+template <int W, bool REFL, int TK>
+struct crc_lane {
+	using T = typename reg<W>::T;
+	static constexpr int NB = W / 8;
+	const T *gt, *r4;
+	uint32_t kidx;
+	T klane, poly, init, xorout;
+
+	template <class P>
+	__device__ __forceinline__ void stage(const P &p, T *s5, T *r4_, int p5x_off, int a5_off, int q4_off,
+					      int a4_off, int nthreads, uint32_t kidx_)
+	{
+		gt = (const T *)p.tbl;
+		r4 = r4_;
+		kidx = kidx_;
+		stage_tables<W, TK>(s5, gt, p5x_off, a5_off, q4_off, a4_off, nthreads);
+		if (REFL && threadIdx.x < 16)
+			r4_[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
+		klane = REFL ? (T)0 : gt[ECG_CSUM_OFF_K64(NB) + kidx];
+		poly = (T)p.poly;
+		init = (T)p.init;
+		xorout = (T)p.xorout;
+	}
+
+	// the lane's final shift: reflected CRCs from the nibl tables (W/4
+	// steps), else mulmod
+	__device__ __forceinline__ T shift(T acc) const
+	{
+		if constexpr (REFL)
+			return lane_mul_nib<W>(acc, gt + ECG_CSUM_OFF_NIBL(NB), r4, kidx);
+		else
+			return mulmod<W, REFL>(klane, acc, poly);
+	}
+
+	// the checksum of a chunk whose nq whole pieces reduced to acc: the
+	// initial register when there was none, then the tail bytes (sl[0] in
+	// memory) and the final XOR
+	__device__ __forceinline__ T finish(T acc, int64_t nq, const uint8_t *base, uint64_t len) const
+	{
+		T crc = nq == 0 ? init : acc;
+
+		for (uint64_t b = (uint64_t)nq * 16; b < len; b++)
+			crc = byte_step<W, REFL>(crc, base[b], gt);
+		return crc ^ xorout;
+	}
+};
+
+// lane steps of a chunk of nq pieces, `per` pieces per step: a multiple of
+// the ECG_CSUM_P5U pieces a Horner step takes
 __device__ __forceinline__ int64_t lane_steps(int64_t nq, int64_t per)
 {
 	const int64_t m = (nq + per - 1) / per;
-	return TK == TK_B8 ? m : (m + ECG_CSUM_P5U - 1) / ECG_CSUM_P5U * ECG_CSUM_P5U;
+	return (m + ECG_CSUM_P5U - 1) / ECG_CSUM_P5U * ECG_CSUM_P5U;
 }
 
 // the U pieces of lane step i (pieces (i+u)*64 + lane - z): `first` masks
@@ -177,81 +187,221 @@ __device__ __forceinline__ void load_step(const uint8_t *base, int64_t i, int64_
 	}
 }
 
+__device__ __forceinline__ void chunk_geom(const ecg_csum_params_t &p, uint64_t g, uint64_t &len,
+					   const uint8_t *&base)
+{
+	const uint64_t e = g / p.nchunks, c = g - e * p.nchunks;
+	const uint64_t off = c == 0 ? 0 : p.first_bytes + (c - 1) * p.chunk_bytes;
+
+	len = c == 0 ? p.first_bytes : p.chunk_bytes;
+	if (off + len > p.ext_bytes)
+		len = p.ext_bytes - off;
+	base = p.src + (int64_t)e * p.ext_stride + off;
+}
+
 // chunk g's geometry with a 32-bit division when the counts allow (the
 // 64-bit one expands to ~100 VALU per chunk)
-__device__ __forceinline__ void chunk_geom_fast(const ecg_csum_params_t &p, uint64_t g, uint64_t &off,
-						uint64_t &len, const uint8_t *&base)
+__device__ __forceinline__ void chunk_geom_fast(const ecg_csum_params_t &p, uint64_t g, uint64_t &len,
+						const uint8_t *&base)
 {
 	if (((g | p.nchunks) >> 32) == 0) {
 		const uint32_t e = (uint32_t)g / p.nchunks, c = (uint32_t)g - e * p.nchunks;
+		const uint64_t off = c == 0 ? 0 : p.first_bytes + (uint64_t)(c - 1) * p.chunk_bytes;
 
-		off = c == 0 ? 0 : p.first_bytes + (uint64_t)(c - 1) * p.chunk_bytes;
 		len = c == 0 ? p.first_bytes : p.chunk_bytes;
 		if (off + len > p.ext_bytes)
 			len = p.ext_bytes - off;
 		base = p.src + (int64_t)e * p.ext_stride + off;
 	} else {
-		chunk_geom(p, g, off, len, base);
+		chunk_geom(p, g, len, base);
 	}
 }
 
-template <int W, bool REFL, bool ALIGNED, int TK>
-__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_kernel(ecg_csum_params_t p)
+// ---------------------------------------------------------------------------
+// Where the work items of a kernel lie and where their checksums go -- all the
+// extent and the masked kernels differ in.  Over the kernel's parameters p:
+// total(p): the items; item(p, g, base, len, slot): the bytes of item g and the
+// slot of its checksum, false when the item is skipped; store<LEN>(p, slot, v):
+// the checksum of LEN bytes; wave(): the wave's index in its block, in a scalar
+// register where the kernel wants its items' geometry on the scalar unit.
+// ---------------------------------------------------------------------------
+
+// The chunks of n_ext extents, item g = chunk g % nchunks of extent g / nchunks
+// (FAST, the CRC kernels: chunk_geom_fast on a scalar g; the adler32 kernels
+// keep the 64-bit division on the vector unit); the checksums are an array of
+// aligned LEN-byte words indexed by g.
+template <bool FAST>
+struct cs_extents {
+	using params = ecg_csum_params_t;
+
+	static __device__ __forceinline__ uint64_t total(const params &p) { return (uint64_t)p.n_ext * p.nchunks; }
+	static __device__ __forceinline__ uint32_t wave()
+	{
+		if constexpr (FAST)
+			return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+		else
+			return threadIdx.x >> 6;
+	}
+	static __device__ __forceinline__ bool item(const params &p, uint64_t g, const uint8_t *&base, uint64_t &len,
+						    uint64_t &slot)
+	{
+		if constexpr (FAST)
+			chunk_geom_fast(p, g, len, base);
+		else
+			chunk_geom(p, g, len, base);
+		slot = g;
+		return true;
+	}
+	template <int LEN, typename T>
+	static __device__ __forceinline__ void store(const params &p, uint64_t slot, T v)
+	{
+		if constexpr (LEN == 2)
+			((uint16_t *)p.out)[slot] = (uint16_t)v;
+		else
+			((T *)p.out)[slot] = v;
+	}
+};
+
+// ecg_csum_masked: the checksums of the cells each stripe's mask word selects
+// (ecg_kabi.h ecg_csum_masked_sel), a wave per (stripe, selected cell, chunk).
+// Item g = (s * slots + r) * nch + c reads masks[s] (wave-uniform), takes the
+// r-th set bit of sel as its cell and is skipped when sel has no r-th bit, so a
+// clean stripe costs its items one load each; the item (s, 0, 0) counts its
+// stripe into result.  Every address derives from sel, which is 0 unless
+// ecg_erasure_set_read reads the word as a set and has no bit at or above
+// k + p: all 2^32 mask values are safe.
+struct cs_masked {
+	using params = ecg_csum_masked_params_t;
+
+	static __device__ __forceinline__ uint64_t total(const params &p)
+	{
+		return (uint64_t)p.nstripes * p.slots * p.nch;
+	}
+	static __device__ __forceinline__ uint32_t wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+	static __device__ __forceinline__ bool item(const params &p, uint64_t g, const uint8_t *&base, uint64_t &len,
+						    uint64_t &slot)
+	{
+		const uint64_t per = (uint64_t)p.slots * p.nch;
+		uint64_t s;
+		uint32_t r, c;
+
+		if (((g | per) >> 32) == 0) {	// as chunk_geom_fast: 32-bit divisions when the counts allow
+			const uint32_t s32 = (uint32_t)g / (uint32_t)per, rem = (uint32_t)g - s32 * (uint32_t)per;
+
+			s = s32;
+			r = rem / p.nch;
+			c = rem - r * p.nch;
+		} else {
+			const uint64_t rem = g % per;
+
+			s = g / per;
+			r = (uint32_t)(rem / p.nch);
+			c = (uint32_t)(rem - (uint64_t)r * p.nch);
+		}
+		const uint32_t m = p.masks[s];
+		int valid;
+		uint32_t sel = ecg_csum_masked_sel(m, (int)p.k, (int)p.p, p.which, &valid);
+
+		if (r == 0 && c == 0 && m != 0 && p.result != nullptr && (threadIdx.x & 63) == 0) {
+			unsigned long long *res = (unsigned long long *)p.result;
+
+			if (valid) {
+				atomicAdd(&res[0], 1ull);
+				atomicAdd(&res[2], (unsigned long long)__builtin_popcount(sel));
+			} else {
+				atomicMin(&res[1], (unsigned long long)s);
+				atomicAdd(&res[3], 1ull);
+			}
+		}
+		if (r >= (uint32_t)__builtin_popcount(sel))
+			return false;
+		for (uint32_t i = 0; i < r; i++)
+			sel &= sel - 1u;
+		const uint32_t cell = (uint32_t)__builtin_ctz(sel);	// < k + p
+		const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
+
+		len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
+		base = p.src + (int64_t)s * p.stripe_stride + (uint64_t)cell * p.cell_bytes + off;
+		slot = (s * (p.k + p.p) + cell) * p.nch + c;
+		return true;
+	}
+	// little-endian; the array may lie at any byte, and a crc16 slot is two
+	// bytes wide: its neighbours may belong to cells that are not selected
+	template <int LEN, typename T>
+	static __device__ __forceinline__ void store(const params &p, uint64_t slot, T v)
+	{
+		uint8_t *at = p.out + slot * LEN;
+
+		if (((uintptr_t)at & (LEN - 1)) == 0) {
+			if constexpr (LEN == 2)
+				*(uint16_t *)at = (uint16_t)v;
+			else
+				*(T *)at = v;
+		} else {
+#pragma unroll
+			for (int b = 0; b < LEN; b++)
+				at[b] = (uint8_t)(v >> (8 * b));
+		}
+	}
+};
+
+// A wave per item (the scheme at the top of the file), blocks striding over
+// the items of Addr.
+template <int W, bool REFL, bool ALIGNED, int TK, class Addr>
+__device__ __forceinline__ void crc_wave(const typename Addr::params &p)
 {
 	using T = typename reg<W>::T;
 	using L = crc_lds<W, TK>;
 	constexpr int NB = W / 8;
 	__shared__ T s5[L::N5];
-	__shared__ T sl[L::NSL];
-	__shared__ T sh[L::NSL];
 	__shared__ T r4[REFL ? 16 : 1];
-	const T *gt = (const T *)p.tbl;
-
-	stage_tables<W, TK>(s5, sl, sh, gt, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
-			    ECG_CSUM_OFF_A4_4K(NB), CS_BLOCK);
-	if (REFL && threadIdx.x < 16)
-		r4[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
 	const int lane = threadIdx.x & 63;
-	const T klane = REFL ? (T)0 : gt[2 * NB * 256 + lane];
-	const T poly = (T)p.poly, init = (T)p.init, xorout = (T)p.xorout;
+	crc_lane<W, REFL, TK> cl;
+
+	cl.stage(p, s5, r4, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
+		 ECG_CSUM_OFF_A4_4K(NB), CS_BLOCK, (uint32_t)lane);
 	__syncthreads();
 
-	const uint64_t total = (uint64_t)p.n_ext * p.nchunks;
-	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+	const uint64_t total = Addr::total(p);
+	const uint32_t wv = Addr::wave();
 	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
-		uint64_t off, len;
+		uint64_t len, slot;
 		const uint8_t *base;
 
-		chunk_geom_fast(p, g, off, len, base);
+		if (!Addr::item(p, g, base, len, slot))
+			continue;
 		const int64_t nq = (int64_t)(len / 16);
-		const int64_t m = lane_steps<TK>(nq, 64);
+		const int64_t m = lane_steps(nq, 64);
 		const int64_t z = m * 64 - nq;
 		T acc = 0;
 
 		if (m > 0) {
 			uint32_t d[L::UN][4];
 
-			load_step<L::UN, W, ALIGNED, true>(base, 0, 64, lane - z, m, init, d);
-			acc = horner<W, REFL, TK, L::UN>(acc, d, 0, m, s5, sl, sh);
+			load_step<L::UN, W, ALIGNED, true>(base, 0, 64, lane - z, m, cl.init, d);
+			acc = horner<W, TK>(acc, d, s5);
 			for (int64_t i = L::UN; i < m; i += L::UN) {
-				load_step<L::UN, W, ALIGNED, TK == TK_B8>(base, i, 64, lane - z, m, init, d);	// byte tables: m need not be a multiple of UN
-				acc = horner<W, REFL, TK, L::UN>(acc, d, i, m, s5, sl, sh);
+				load_step<L::UN, W, ALIGNED, false>(base, i, 64, lane - z, m, cl.init, d);
+				acc = horner<W, TK>(acc, d, s5);
 			}
 		}
-		acc = lane_shift<W, REFL>(acc, klane, gt, r4, (uint32_t)lane, poly);
+		acc = cl.shift(acc);
 		acc = wave_xor_uniform(acc);	// DPP, no ds_bpermute
-		if (lane == 0) {
-			T crc = nq == 0 ? init : acc;
-
-			for (uint64_t b = (uint64_t)nq * 16; b < len; b++)	// tail bytes: sl[0] in memory
-				crc = byte_step<W, REFL>(crc, base[b], gt);
-			crc ^= xorout;
-			if constexpr (W == 16)
-				((uint16_t *)p.out)[g] = (uint16_t)crc;
-			else
-				((T *)p.out)[g] = crc;
-		}
+		if (lane == 0)
+			Addr::template store<NB>(p, slot, cl.finish(acc, nq, base, len));
 	}
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_kernel(ecg_csum_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_extents<true>>(p);
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_kernel(ecg_csum_masked_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_masked>(p);
 }
 
 template <typename T>
@@ -268,9 +418,9 @@ __device__ __forceinline__ T shfl_xor_t(T v, int s)
 // pieces and the per-lane final multiply (W GF(2) steps) dominates.  Here a
 // group of G = ECG_CSUM_GLANES lanes takes a chunk (4 chunks per wave): lane
 // l of the group takes pieces q = G*i + l - z, so each load instruction still
-// reads 4 x 256 B contiguous, Horner-steps by G*16 bytes (sh256 table), and
-// the group reduces with shuffles after multiplying by x^(8*16*(G-1-l)) =
-// k64[64 - G + l].  Otherwise as ecg_crc_kernel.
+// reads 4 x 256 B contiguous, Horner-steps by G*16 bytes (the 256 B stride's
+// tables), and the group reduces with shuffles after multiplying by
+// x^(8*16*(G-1-l)) = k64[64 - G + l].  Otherwise as crc_wave.
 template <int W, bool REFL, int TK>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_group_kernel(ecg_csum_params_t p)
 {
@@ -280,28 +430,16 @@ __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_group_kernel(ecg_csum_params
 	constexpr int G = ECG_CSUM_GLANES;
 	constexpr int GPW = 64 / G;		// chunks per wave
 	__shared__ T s5[L::N5];
-	__shared__ T sl[L::NSL];
-	__shared__ T sh[L::NSL];
 	__shared__ T r4[REFL ? 16 : 1];
-	const T *gt = (const T *)p.tbl;
-
-	if constexpr (TK == TK_B8) {
-		for (int i = threadIdx.x; i < NB * 256; i += CS_BLOCK) {
-			sl[i] = gt[i];
-			sh[i] = gt[ECG_CSUM_OFF_SH256(NB) + i];
-		}
-	} else {
-		stage_tables<W, TK>(s5, sl, sh, gt, ECG_CSUM_OFF_P5X_256(NB), ECG_CSUM_OFF_A5_1K(NB),
-				    ECG_CSUM_OFF_Q4_256(NB), ECG_CSUM_OFF_A4_1K(NB), CS_BLOCK);
-	}
-	if (REFL && threadIdx.x < 16)
-		r4[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
 	const int lane = threadIdx.x & 63, gl = lane % G;
-	const T klane = gt[ECG_CSUM_OFF_K64(NB) + 64 - G + gl];
-	const T poly = (T)p.poly, init = (T)p.init, xorout = (T)p.xorout;
+	using Addr = cs_extents<true>;
+	crc_lane<W, REFL, TK> cl;
+
+	cl.stage(p, s5, r4, ECG_CSUM_OFF_P5X_256(NB), ECG_CSUM_OFF_A5_1K(NB), ECG_CSUM_OFF_Q4_256(NB),
+		 ECG_CSUM_OFF_A4_1K(NB), CS_BLOCK, (uint32_t)(64 - G + gl));
 	__syncthreads();
 
-	const uint64_t total = (uint64_t)p.n_ext * p.nchunks;
+	const uint64_t total = Addr::total(p);
 	const uint64_t waves = (uint64_t)gridDim.x * CS_WAVES;
 	// every lane runs the same number of outer iterations (shuffles below
 	// need the whole wave): the wave's first chunk decides, idle groups mask
@@ -309,40 +447,30 @@ __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_group_kernel(ecg_csum_params
 	     g0 += waves * GPW) {
 		const uint64_t g = g0 + lane / G;
 		const bool live = g < total;
-		uint64_t off = 0, len = 0;
+		uint64_t len = 0, slot = g;
 		const uint8_t *base = p.src;
 
 		if (live)
-			chunk_geom_fast(p, g, off, len, base);
+			Addr::item(p, g, base, len, slot);
 		const int64_t nq = (int64_t)(len / 16);
-		const int64_t m = lane_steps<TK>(nq, G);
+		const int64_t m = lane_steps(nq, G);
 		const int64_t z = m * G - nq;
 		T acc = 0;
 
 		for (int64_t i = 0; i < m; i += L::UN) {
 			uint32_t d[L::UN][4];
 
-			load_step<L::UN, W, true, true>(base, i, G, gl - z, m, init, d);
-			acc = horner<W, REFL, TK, L::UN>(acc, d, i, m, s5, sl, sh);
+			load_step<L::UN, W, true, true>(base, i, G, gl - z, m, cl.init, d);
+			acc = horner<W, TK>(acc, d, s5);
 		}
-		acc = lane_shift<W, REFL>(acc, klane, gt, r4, (uint32_t)(64 - G + gl), poly);
+		acc = cl.shift(acc);
 #pragma unroll
 		for (int s = G / 2; s >= 1; s >>= 1)
 			acc ^= shfl_xor_t(acc, s);
-		if (live && gl == 0) {
-			T crc = nq == 0 ? init : acc;
-
-			for (uint64_t b = (uint64_t)nq * 16; b < len; b++)
-				crc = byte_step<W, REFL>(crc, base[b], gt);
-			crc ^= xorout;
-			if constexpr (W == 16)
-				((uint16_t *)p.out)[g] = (uint16_t)crc;
-			else
-				((T *)p.out)[g] = crc;
-		}
+		if (live && gl == 0)
+			Addr::template store<NB>(p, slot, cl.finish(acc, nq, base, len));
 	}
 }
-
 
 // Long chunks, few of them (e.g. 1024 chunks of 1 MiB = one wave per SIMD
 // with ecg_crc_kernel): one workgroup of NW waves per chunk.  The chunk's
@@ -360,29 +488,24 @@ __global__ __launch_bounds__(64 * NW) void ecg_crc_split_kernel(ecg_csum_params_
 	using L = crc_lds<W, TK>;
 	constexpr int NB = W / 8;
 	__shared__ T s5[L::N5];
-	__shared__ T sl[L::NSL];
-	__shared__ T sh[L::NSL];
 	__shared__ T part[NW];
 	__shared__ T r4[REFL ? 16 : 1];
-	const T *gt = (const T *)p.tbl;
-
-	stage_tables<W, TK>(s5, sl, sh, gt, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
-			    ECG_CSUM_OFF_A4_4K(NB), 64 * NW);
-	if (REFL && threadIdx.x < 16)
-		r4[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	const T klane = gt[2 * NB * 256 + lane];
+	using Addr = cs_extents<true>;
+	crc_lane<W, REFL, TK> cl;
+
+	cl.stage(p, s5, r4, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
+		 ECG_CSUM_OFF_A4_4K(NB), 64 * NW, (uint32_t)lane);
 	const T one = REFL ? (T)((T)1 << (W - 1)) : (T)1;
-	const T p2 = lane < ECG_CSUM_NP2 ? gt[ECG_CSUM_OFF_P2(NB) + lane] : one;
-	const T poly = (T)p.poly, init = (T)p.init, xorout = (T)p.xorout;
+	const T p2 = lane < ECG_CSUM_NP2 ? cl.gt[ECG_CSUM_OFF_P2(NB) + lane] : one;
 	__syncthreads();
 
-	const uint64_t total = (uint64_t)p.n_ext * p.nchunks;
+	const uint64_t total = Addr::total(p);
 	for (uint64_t g = blockIdx.x; g < total; g += gridDim.x) {
-		uint64_t off, len;
+		uint64_t len, slot;
 		const uint8_t *base;
 
-		chunk_geom_fast(p, g, off, len, base);
+		Addr::item(p, g, base, len, slot);
 		static_assert(NW == ECG_CSUM_SPLIT_NW, "host split shifts assume ECG_CSUM_SPLIT_NW slices");
 		const int64_t nq = (int64_t)(len / 16);
 		const int64_t m = (int64_t)ECG_CSUM_STEPS((uint64_t)len);	// as the host's split_m
@@ -395,10 +518,10 @@ __global__ __launch_bounds__(64 * NW) void ecg_crc_split_kernel(ecg_csum_params_
 		for (int64_t i = i0; i < i1; i += L::UN) {
 			uint32_t d[L::UN][4];
 
-			load_step<L::UN, W, true, true>(base, i, 64, lane - z, i1, init, d);
-			acc = horner<W, REFL, TK, L::UN>(acc, d, i, i1, s5, sl, sh);
+			load_step<L::UN, W, true, true>(base, i, 64, lane - z, i1, cl.init, d);
+			acc = horner<W, TK>(acc, d, s5);
 		}
-		acc = lane_shift<W, REFL>(acc, klane, gt, r4, (uint32_t)lane, poly);
+		acc = cl.shift(acc);
 		acc = wave_xor_uniform(acc);	// DPP, no ds_bpermute
 		// x^(8 * (m - i1) KiB): the host's constant for this chunk length,
 		// else the product of p2[j] over the set bits j (one bit per lane)
@@ -411,9 +534,9 @@ __global__ __launch_bounds__(64 * NW) void ecg_crc_split_kernel(ecg_csum_params_
 			f = lane < ECG_CSUM_NP2 && ((after >> lane) & 1) ? p2 : one;
 #pragma unroll
 			for (int s = 32; s >= 1; s >>= 1)
-				f = mulmod<W, REFL>(f, shfl_xor_t(f, s), poly);
+				f = mulmod<W, REFL>(f, shfl_xor_t(f, s), cl.poly);
 		}
-		acc = mulmod<W, REFL>(f, acc, poly);
+		acc = mulmod<W, REFL>(f, acc, cl.poly);
 		if (lane == 0)
 			part[wv] = acc;
 		__syncthreads();
@@ -423,15 +546,7 @@ __global__ __launch_bounds__(64 * NW) void ecg_crc_split_kernel(ecg_csum_params_
 #pragma unroll
 			for (int w = 0; w < NW; w++)
 				crc ^= part[w];
-			if (nq == 0)
-				crc = init;
-			for (uint64_t b = (uint64_t)nq * 16; b < len; b++)
-				crc = byte_step<W, REFL>(crc, base[b], gt);
-			crc ^= xorout;
-			if constexpr (W == 16)
-				((uint16_t *)p.out)[g] = (uint16_t)crc;
-			else
-				((T *)p.out)[g] = crc;
+			Addr::template store<NB>(p, slot, cl.finish(crc, nq, base, len));
 		}
 		__syncthreads();
 	}
@@ -440,58 +555,95 @@ __global__ __launch_bounds__(64 * NW) void ecg_crc_split_kernel(ecg_csum_params_
 // adler32 with A = B = 0 at each chunk start (isal_adler32(0, ...)): lanes sum
 // bytes and position-weighted bytes of their pieces (v_dot4_u32_u8), the wave
 // reduces, A = sum mod 65521, B = L*sum - sum(pos*byte) mod 65521.
+
+// a lane's sums over the pieces q0, q0 + stride, ... below nq, each mod 65521
+// (reduced every 256 pieces: a piece adds < 2^12 to s and < 2^16 * len to w)
+template <bool ALIGNED>
+__device__ __forceinline__ void adler_lane(const uint8_t *base, uint64_t nq, uint64_t q0, uint64_t stride,
+					   uint64_t &s, uint64_t &w)
+{
+	s = 0;
+	w = 0;
+	for (uint64_t q = q0, it = 0; q < nq; q += stride, it++) {
+		uint32_t d[4];
+		uint32_t s16 = 0, w16 = 0;
+
+		load16<ALIGNED>(base + 16 * q, d);
+#pragma unroll
+		for (int j = 0; j < 4; j++) {
+			s16 = __builtin_amdgcn_udot4(d[j], 0x01010101u, s16, false);
+			// weights 4j .. 4j+3 packed as bytes
+			w16 = __builtin_amdgcn_udot4(d[j], 0x03020100u + 0x04040404u * j, w16, false);
+		}
+		s += s16;
+		w += 16 * q * (uint64_t)s16 + w16;
+		if ((it & 255) == 255) {
+			s %= ADLER_MOD;
+			w %= ADLER_MOD;
+		}
+	}
+	s %= ADLER_MOD;
+	w %= ADLER_MOD;
+}
+
+// wave sum (values < 2^17 each: 64 of them fit easily)
+__device__ __forceinline__ void adler_wave_sum(uint64_t &s, uint64_t &w)
+{
+#pragma unroll
+	for (int sft = 32; sft >= 1; sft >>= 1) {
+		s += __shfl_xor(s, sft);
+		w += __shfl_xor(w, sft);
+	}
+}
+
+// the checksum of a chunk of len bytes whose nq whole pieces summed to (s, w):
+// the tail bytes, then A and B packed
+__device__ __forceinline__ uint32_t adler_finish(uint64_t s, uint64_t w, const uint8_t *base, uint64_t nq,
+						 uint64_t len)
+{
+	for (uint64_t b = nq * 16; b < len; b++) {
+		s += base[b];
+		w += b * (uint64_t)base[b];
+	}
+	const uint64_t A = s % ADLER_MOD;
+	const uint64_t Bp = ((len % ADLER_MOD) * A) % ADLER_MOD;
+	const uint64_t B = (Bp + ADLER_MOD - w % ADLER_MOD) % ADLER_MOD;
+	return (uint32_t)((B << 16) | A);
+}
+
+// A wave per item, as crc_wave.
+template <bool ALIGNED, class Addr>
+__device__ __forceinline__ void adler_wave(const typename Addr::params &p)
+{
+	const int lane = threadIdx.x & 63;
+	const uint64_t total = Addr::total(p);
+	const uint32_t wv = Addr::wave();
+
+	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
+		uint64_t len, slot, s, w;
+		const uint8_t *base;
+
+		if (!Addr::item(p, g, base, len, slot))
+			continue;
+		const uint64_t nq = len / 16;
+
+		adler_lane<ALIGNED>(base, nq, lane, 64, s, w);
+		adler_wave_sum(s, w);
+		if (lane == 0)
+			Addr::template store<4>(p, slot, adler_finish(s, w, base, nq, len));
+	}
+}
+
 template <bool ALIGNED>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_adler_kernel(ecg_csum_params_t p)
 {
-	const int lane = threadIdx.x & 63;
-	const uint64_t total = (uint64_t)p.n_ext * p.nchunks;
+	adler_wave<ALIGNED, cs_extents<false>>(p);
+}
 
-	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + (threadIdx.x >> 6); g < total;
-	     g += (uint64_t)gridDim.x * CS_WAVES) {
-		uint64_t off, len;
-		const uint8_t *base;
-
-		chunk_geom(p, g, off, len, base);
-		const uint64_t nq = len / 16;
-		uint64_t s = 0, w = 0;
-
-		for (uint64_t q = lane, it = 0; q < nq; q += 64, it++) {
-			uint32_t d[4];
-			uint32_t s16 = 0, w16 = 0;
-
-			load16<ALIGNED>(base + 16 * q, d);
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				s16 = __builtin_amdgcn_udot4(d[j], 0x01010101u, s16, false);
-				// weights 4j .. 4j+3 packed as bytes
-				w16 = __builtin_amdgcn_udot4(d[j], 0x03020100u + 0x04040404u * j, w16, false);
-			}
-			s += s16;
-			w += 16 * q * (uint64_t)s16 + w16;
-			if ((it & 255) == 255) {
-				s %= ADLER_MOD;
-				w %= ADLER_MOD;
-			}
-		}
-		s %= ADLER_MOD;
-		w %= ADLER_MOD;
-		// wave sum (values < 2^17 each: 64 of them fit easily)
-#pragma unroll
-		for (int sft = 32; sft >= 1; sft >>= 1) {
-			s += __shfl_xor(s, sft);
-			w += __shfl_xor(w, sft);
-		}
-		if (lane == 0) {
-			for (uint64_t b = nq * 16; b < len; b++) {
-				s += base[b];
-				w += b * (uint64_t)base[b];
-			}
-			const uint64_t A = s % ADLER_MOD;
-			const uint64_t Bp = ((len % ADLER_MOD) * A) % ADLER_MOD;
-			const uint64_t B = (Bp + ADLER_MOD - w % ADLER_MOD) % ADLER_MOD;
-			((uint32_t *)p.out)[g] = (uint32_t)((B << 16) | A);
-		}
-	}
+template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_kernel(ecg_csum_masked_params_t p)
+{
+	adler_wave<ALIGNED, cs_masked>(p);
 }
 
 // adler32 of long chunks that are few (one wave per chunk would leave the
@@ -505,35 +657,20 @@ __global__ __launch_bounds__(64 * NW) void ecg_adler_split_kernel(ecg_csum_param
 {
 	__shared__ uint64_t ps[NW], pw[NW];
 	const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-	const uint64_t total = (uint64_t)p.n_ext * p.nchunks;
+	using Addr = cs_extents<false>;
+	const uint64_t total = Addr::total(p);
 
 	for (uint64_t g = blockIdx.x; g < total; g += gridDim.x) {
-		uint64_t off, len;
+		uint64_t len, slot, s, w;
 		const uint8_t *base;
 
-		chunk_geom(p, g, off, len, base);
+		Addr::item(p, g, base, len, slot);
 		const uint64_t nq = len / 16;
-		uint64_t s = 0, w = 0;
 
-		for (uint64_t q = threadIdx.x, it = 0; q < nq; q += 64 * NW, it++) {
-			uint32_t d[4];
-			uint32_t s16 = 0, w16 = 0;
-
-			load16<true>(base + 16 * q, d);
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				s16 = __builtin_amdgcn_udot4(d[j], 0x01010101u, s16, false);
-				w16 = __builtin_amdgcn_udot4(d[j], 0x03020100u + 0x04040404u * j, w16, false);
-			}
-			s += s16;
-			w += 16 * q * (uint64_t)s16 + w16;
-			if ((it & 255) == 255) {
-				s %= ADLER_MOD;
-				w %= ADLER_MOD;
-			}
-		}
-		s %= ADLER_MOD;
-		w %= ADLER_MOD;
+		adler_lane<true>(base, nq, threadIdx.x, 64 * NW, s, w);
+		// adler_wave_sum and, below, adler_finish written out: behind the
+		// helpers this kernel is not the code it was (the finish keeps
+		// thread 0's sums in vector registers, 2 more VGPRs)
 #pragma unroll
 		for (int sft = 32; sft >= 1; sft >>= 1) {
 			s += __shfl_xor(s, sft);
@@ -559,56 +696,10 @@ __global__ __launch_bounds__(64 * NW) void ecg_adler_split_kernel(ecg_csum_param
 			const uint64_t A = s % ADLER_MOD;
 			const uint64_t Bp = ((len % ADLER_MOD) * A) % ADLER_MOD;
 			const uint64_t B = (Bp + ADLER_MOD - w % ADLER_MOD) % ADLER_MOD;
-			((uint32_t *)p.out)[g] = (uint32_t)((B << 16) | A);
+			Addr::template store<4>(p, slot, (uint32_t)((B << 16) | A));
 		}
 		__syncthreads();
 	}
-}
-
-typedef void (*csum_fn_t)(ecg_csum_params_t);
-struct csum_entry {
-	uint32_t type;
-	bool aligned;
-	int tk;			/* CRC table kind (TK_*); adler32: 0 */
-	csum_fn_t fn;
-	const char *name;
-};
-
-const csum_entry g_csum[] = {
-	{1, true, TK_4, ecg_crc_kernel<16, false, true, TK_4>, "ecg_crc_kernel<crc16>"},
-	{1, false, TK_5, ecg_crc_kernel<16, false, false, TK_5>, "ecg_crc_kernel<crc16,bytes>"},
-	{2, true, TK_4, ecg_crc_kernel<32, true, true, TK_4>, "ecg_crc_kernel<crc32>"},
-	{2, false, TK_5, ecg_crc_kernel<32, true, false, TK_5>, "ecg_crc_kernel<crc32,bytes>"},
-	{3, true, TK_4, ecg_crc_kernel<64, true, true, TK_4>, "ecg_crc_kernel<crc64>"},
-	{3, false, TK_5, ecg_crc_kernel<64, true, false, TK_5>, "ecg_crc_kernel<crc64,bytes>"},
-	{7, true, 0, ecg_adler_kernel<true>, "ecg_adler_kernel"},
-	{7, false, 0, ecg_adler_kernel<false>, "ecg_adler_kernel<bytes>"},
-};
-constexpr uint32_t N_CSUM = sizeof(g_csum) / sizeof(g_csum[0]);
-
-constexpr int SPLIT_NW = ECG_CSUM_SPLIT_NW;	// waves per chunk in the split kernel
-const csum_entry g_split[] = {
-	{1, true, TK_4, ecg_crc_split_kernel<16, false, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc16>"},
-	{2, true, TK_4, ecg_crc_split_kernel<32, true, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc32>"},
-	{3, true, TK_4, ecg_crc_split_kernel<64, true, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc64>"},
-	{7, true, 0, ecg_adler_split_kernel<SPLIT_NW>, "ecg_adler_split_kernel"},
-};
-constexpr uint32_t N_SPLIT = sizeof(g_split) / sizeof(g_split[0]);
-
-const csum_entry g_group[] = {
-	{1, true, TK_4, ecg_crc_group_kernel<16, false, TK_4>, "ecg_crc_group_kernel<crc16>"},
-	{2, true, TK_4, ecg_crc_group_kernel<32, true, TK_4>, "ecg_crc_group_kernel<crc32>"},
-	{3, true, TK_4, ecg_crc_group_kernel<64, true, TK_4>, "ecg_crc_group_kernel<crc64>"},
-};
-constexpr uint32_t N_GROUP = sizeof(g_group) / sizeof(g_group[0]);
-
-/* one table kind per kernel: the nibble tables for 16-byte aligned extents,
- * the 5-bit tables for the byte-granular kernels (the byte and 5-bit aligned
- * variants of rounds 1-3 were A/B builds, profiles/r03/crc_sq/) */
-__host__ inline bool kind_ok(const csum_entry &e, const ecg_csum_params_t *p)
-{
-	(void)p;
-	return e.type == 7 || e.tk == (e.aligned ? TK_4 : TK_5);
 }
 
 // Compare n checksums of LEN bytes (ecg_csum_compare): grid-stride, each
@@ -638,7 +729,6 @@ ecg_csum_compare_kernel(const uint8_t *got, const uint8_t *want, uint64_t n, uns
 		atomicMin(&result[1], lo);
 	}
 }
-constexpr uint32_t KID_COMPARE = ECG_KID_CSUM + N_CSUM + N_SPLIT + N_GROUP;
 
 // Which cells' checksums differ, per stripe (ecg_csum_mask): a thread takes
 // one (stripe, cell) and compares its nch checksums of LEN bytes; a cell with
@@ -661,208 +751,45 @@ ecg_csum_mask_kernel(const uint8_t *got, const uint8_t *want, uint32_t nstripes,
 			atomicOr(&masks[s], 1u << (first_cell + i));
 	}
 }
-constexpr uint32_t KID_MASK = KID_COMPARE + 1;
 
-// ---------------------------------------------------------------------------
-// ecg_csum_masked: the checksums of the cells each stripe's mask word selects
-// (ecg_kabi.h ecg_csum_masked_sel), a wave per (stripe, selected cell, chunk).
-// Only the geometry differs from ecg_crc_kernel / ecg_adler_kernel: item g =
-// (s * slots + r) * nch + c reads masks[s] (wave-uniform), takes the r-th set
-// bit of sel as its cell and is skipped when sel has no r-th bit, so a clean
-// stripe costs its items one load each.  Every address derives from sel, which
-// is 0 unless ecg_erasure_set_read reads the word as a set and has no bit at or
-// above k + p: all 2^32 mask values are safe.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ bool masked_geom(const ecg_csum_masked_params_t &p, uint64_t g, const uint8_t *&base,
-					    uint64_t &len, uint64_t &slot)
-{
-	const uint64_t per = (uint64_t)p.slots * p.nch;
-	uint64_t s;
-	uint32_t r, c;
-
-	if (((g | per) >> 32) == 0) {	// as chunk_geom_fast: 32-bit divisions when the counts allow
-		const uint32_t s32 = (uint32_t)g / (uint32_t)per, rem = (uint32_t)g - s32 * (uint32_t)per;
-
-		s = s32;
-		r = rem / p.nch;
-		c = rem - r * p.nch;
-	} else {
-		const uint64_t rem = g % per;
-
-		s = g / per;
-		r = (uint32_t)(rem / p.nch);
-		c = (uint32_t)(rem - (uint64_t)r * p.nch);
-	}
-	const uint32_t m = p.masks[s];
-	int valid;
-	uint32_t sel = ecg_csum_masked_sel(m, (int)p.k, (int)p.p, p.which, &valid);
-
-	if (r == 0 && c == 0 && m != 0 && p.result != nullptr && (threadIdx.x & 63) == 0) {
-		unsigned long long *res = (unsigned long long *)p.result;
-
-		if (valid) {
-			atomicAdd(&res[0], 1ull);
-			atomicAdd(&res[2], (unsigned long long)__builtin_popcount(sel));
-		} else {
-			atomicMin(&res[1], (unsigned long long)s);
-			atomicAdd(&res[3], 1ull);
-		}
-	}
-	if (r >= (uint32_t)__builtin_popcount(sel))
-		return false;
-	for (uint32_t i = 0; i < r; i++)
-		sel &= sel - 1u;
-	const uint32_t cell = (uint32_t)__builtin_ctz(sel);	// < k + p
-	const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
-
-	len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
-	base = p.src + (int64_t)s * p.stripe_stride + (uint64_t)cell * p.cell_bytes + off;
-	slot = (s * (p.k + p.p) + cell) * p.nch + c;
-	return true;
-}
-
-// One checksum of LEN bytes at slot `slot`, little-endian; the array may lie
-// at any byte, and a crc16 slot is two bytes wide: its neighbours may belong
-// to cells that are not selected.
-template <int LEN, typename T>
-__device__ __forceinline__ void masked_store(uint8_t *out, uint64_t slot, T v)
-{
-	uint8_t *at = out + slot * LEN;
-
-	if (((uintptr_t)at & (LEN - 1)) == 0) {
-		if constexpr (LEN == 2)
-			*(uint16_t *)at = (uint16_t)v;
-		else
-			*(T *)at = v;
-	} else {
-#pragma unroll
-		for (int b = 0; b < LEN; b++)
-			at[b] = (uint8_t)(v >> (8 * b));
-	}
-}
-
-template <int W, bool REFL, bool ALIGNED, int TK>
-__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_kernel(ecg_csum_masked_params_t p)
-{
-	using T = typename reg<W>::T;
-	using L = crc_lds<W, TK>;
-	constexpr int NB = W / 8;
-	static_assert(TK != TK_B8, "m is a multiple of UN below");
-	__shared__ T s5[L::N5];
-	__shared__ T sl[L::NSL];
-	__shared__ T sh[L::NSL];
-	__shared__ T r4[REFL ? 16 : 1];
-	const T *gt = (const T *)p.tbl;
-
-	stage_tables<W, TK>(s5, sl, sh, gt, ECG_CSUM_OFF_P5X_1K(NB), ECG_CSUM_OFF_A5_4K(NB), ECG_CSUM_OFF_Q4_1K(NB),
-			    ECG_CSUM_OFF_A4_4K(NB), CS_BLOCK);
-	if (REFL && threadIdx.x < 16)
-		r4[threadIdx.x] = gt[ECG_CSUM_OFF_R4(NB) + threadIdx.x];
-	const int lane = threadIdx.x & 63;
-	const T klane = REFL ? (T)0 : gt[2 * NB * 256 + lane];
-	const T poly = (T)p.poly, init = (T)p.init, xorout = (T)p.xorout;
-	__syncthreads();
-
-	const uint64_t total = (uint64_t)p.nstripes * p.slots * p.nch;
-	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
-		uint64_t len, slot;
-		const uint8_t *base;
-
-		if (!masked_geom(p, g, base, len, slot))
-			continue;
-		const int64_t nq = (int64_t)(len / 16);
-		const int64_t m = lane_steps<TK>(nq, 64);
-		const int64_t z = m * 64 - nq;
-		T acc = 0;
-
-		if (m > 0) {
-			uint32_t d[L::UN][4];
-
-			load_step<L::UN, W, ALIGNED, true>(base, 0, 64, lane - z, m, init, d);
-			acc = horner<W, REFL, TK, L::UN>(acc, d, 0, m, s5, sl, sh);
-			for (int64_t i = L::UN; i < m; i += L::UN) {
-				load_step<L::UN, W, ALIGNED, false>(base, i, 64, lane - z, m, init, d);
-				acc = horner<W, REFL, TK, L::UN>(acc, d, i, m, s5, sl, sh);
-			}
-		}
-		acc = lane_shift<W, REFL>(acc, klane, gt, r4, (uint32_t)lane, poly);
-		acc = wave_xor_uniform(acc);
-		if (lane == 0) {
-			T crc = nq == 0 ? init : acc;
-
-			for (uint64_t b = (uint64_t)nq * 16; b < len; b++)	// tail bytes: sl[0] in memory
-				crc = byte_step<W, REFL>(crc, base[b], gt);
-			crc ^= xorout;
-			masked_store<NB>(p.out, slot, crc);
-		}
-	}
-}
-
-template <bool ALIGNED>
-__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_kernel(ecg_csum_masked_params_t p)
-{
-	const int lane = threadIdx.x & 63;
-	const uint64_t total = (uint64_t)p.nstripes * p.slots * p.nch;
-	const uint32_t wv = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-
-	for (uint64_t g = (uint64_t)blockIdx.x * CS_WAVES + wv; g < total; g += (uint64_t)gridDim.x * CS_WAVES) {
-		uint64_t len, slot;
-		const uint8_t *base;
-
-		if (!masked_geom(p, g, base, len, slot))
-			continue;
-		const uint64_t nq = len / 16;
-		uint64_t s = 0, w = 0;
-
-		for (uint64_t q = lane, it = 0; q < nq; q += 64, it++) {
-			uint32_t d[4];
-			uint32_t s16 = 0, w16 = 0;
-
-			load16<ALIGNED>(base + 16 * q, d);
-#pragma unroll
-			for (int j = 0; j < 4; j++) {
-				s16 = __builtin_amdgcn_udot4(d[j], 0x01010101u, s16, false);
-				w16 = __builtin_amdgcn_udot4(d[j], 0x03020100u + 0x04040404u * j, w16, false);
-			}
-			s += s16;
-			w += 16 * q * (uint64_t)s16 + w16;
-			if ((it & 255) == 255) {
-				s %= ADLER_MOD;
-				w %= ADLER_MOD;
-			}
-		}
-		s %= ADLER_MOD;
-		w %= ADLER_MOD;
-#pragma unroll
-		for (int sft = 32; sft >= 1; sft >>= 1) {
-			s += __shfl_xor(s, sft);
-			w += __shfl_xor(w, sft);
-		}
-		if (lane == 0) {
-			for (uint64_t b = nq * 16; b < len; b++) {
-				s += base[b];
-				w += b * (uint64_t)base[b];
-			}
-			const uint64_t A = s % ADLER_MOD;
-			const uint64_t Bp = ((len % ADLER_MOD) * A) % ADLER_MOD;
-			const uint64_t B = (Bp + ADLER_MOD - w % ADLER_MOD) % ADLER_MOD;
-			masked_store<4>(p.out, slot, (uint32_t)((B << 16) | A));
-		}
-	}
-}
-
-typedef void (*masked_fn_t)(ecg_csum_masked_params_t);
-struct masked_entry {
+// One table per kernel family, a row per (hash type, 16-byte aligned or not);
+// a kernel's id is its table's first id plus its row.  One table kind per
+// kernel: the nibble tables for 16-byte aligned chunks, the 5-bit tables for
+// the byte-granular kernels.
+template <class P>
+struct csum_entry {
 	uint32_t type;
 	bool aligned;
-	masked_fn_t fn;
+	void (*fn)(P);
 	const char *name;
 };
 
-// the table kinds of g_csum: nibble tables for 16-byte aligned chunks, 5-bit
-// tables for the byte-granular variants
-const masked_entry g_masked[] = {
+const csum_entry<ecg_csum_params_t> g_csum[] = {
+	{1, true, ecg_crc_kernel<16, false, true, TK_4>, "ecg_crc_kernel<crc16>"},
+	{1, false, ecg_crc_kernel<16, false, false, TK_5>, "ecg_crc_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_kernel<32, true, true, TK_4>, "ecg_crc_kernel<crc32>"},
+	{2, false, ecg_crc_kernel<32, true, false, TK_5>, "ecg_crc_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_kernel<64, true, true, TK_4>, "ecg_crc_kernel<crc64>"},
+	{3, false, ecg_crc_kernel<64, true, false, TK_5>, "ecg_crc_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_kernel<true>, "ecg_adler_kernel"},
+	{7, false, ecg_adler_kernel<false>, "ecg_adler_kernel<bytes>"},
+};
+
+constexpr int SPLIT_NW = ECG_CSUM_SPLIT_NW;	// waves per chunk in the split kernel
+const csum_entry<ecg_csum_params_t> g_split[] = {
+	{1, true, ecg_crc_split_kernel<16, false, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc16>"},
+	{2, true, ecg_crc_split_kernel<32, true, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc32>"},
+	{3, true, ecg_crc_split_kernel<64, true, SPLIT_NW, TK_4>, "ecg_crc_split_kernel<crc64>"},
+	{7, true, ecg_adler_split_kernel<SPLIT_NW>, "ecg_adler_split_kernel"},
+};
+
+const csum_entry<ecg_csum_params_t> g_group[] = {
+	{1, true, ecg_crc_group_kernel<16, false, TK_4>, "ecg_crc_group_kernel<crc16>"},
+	{2, true, ecg_crc_group_kernel<32, true, TK_4>, "ecg_crc_group_kernel<crc32>"},
+	{3, true, ecg_crc_group_kernel<64, true, TK_4>, "ecg_crc_group_kernel<crc64>"},
+};
+
+const csum_entry<ecg_csum_masked_params_t> g_masked[] = {
 	{1, true, ecg_crc_masked_kernel<16, false, true, TK_4>, "ecg_crc_masked_kernel<crc16>"},
 	{1, false, ecg_crc_masked_kernel<16, false, false, TK_5>, "ecg_crc_masked_kernel<crc16,bytes>"},
 	{2, true, ecg_crc_masked_kernel<32, true, true, TK_4>, "ecg_crc_masked_kernel<crc32>"},
@@ -872,8 +799,50 @@ const masked_entry g_masked[] = {
 	{7, true, ecg_adler_masked_kernel<true>, "ecg_adler_masked_kernel"},
 	{7, false, ecg_adler_masked_kernel<false>, "ecg_adler_masked_kernel<bytes>"},
 };
-constexpr uint32_t N_MASKED = sizeof(g_masked) / sizeof(g_masked[0]);
+
+template <class E, uint32_t N>
+constexpr uint32_t rows(const E (&)[N])
+{
+	return N;
+}
+constexpr uint32_t KID_SPLIT = ECG_KID_CSUM + rows(g_csum);
+constexpr uint32_t KID_GROUP = KID_SPLIT + rows(g_split);
+constexpr uint32_t KID_COMPARE = KID_GROUP + rows(g_group);
+constexpr uint32_t KID_MASK = KID_COMPARE + 1;
 constexpr uint32_t KID_MASKED = KID_MASK + 1;
+
+template <auto &T>
+const char *row_name(uint32_t i)
+{
+	return T[i].name;
+}
+const struct {
+	uint32_t first, n;
+	const char *(*name)(uint32_t row);
+} g_ids[] = {
+	{ECG_KID_CSUM, rows(g_csum), row_name<g_csum>},
+	{KID_SPLIT, rows(g_split), row_name<g_split>},
+	{KID_GROUP, rows(g_group), row_name<g_group>},
+	{KID_MASKED, rows(g_masked), row_name<g_masked>},
+};
+
+// Launch the (type, aligned) row of table t, whose ids start at `first`, on
+// min(nb, cap) blocks of `threads` and report its id.
+template <class P, uint32_t N>
+int launch_row(const csum_entry<P> (&t)[N], uint32_t first, bool aligned, uint64_t nb, uint64_t cap,
+	       uint32_t threads, const P *p, void *stream, uint32_t *kernel_id)
+{
+	for (uint32_t i = 0; i < N; i++) {
+		if (t[i].type != p->type || t[i].aligned != aligned)
+			continue;
+		hipLaunchKernelGGL(t[i].fn, dim3((uint32_t)(nb < cap ? nb : cap)), dim3(threads), 0,
+				   (hipStream_t)stream, *p);
+		if (kernel_id)
+			*kernel_id = first + i;
+		return (int)hipGetLastError();
+	}
+	return (int)hipErrorInvalidValue;
+}
 
 } // namespace
 
@@ -884,7 +853,6 @@ extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void 
 	// the chunks of every cell start 16-byte aligned only when all four are
 	const bool aligned = (((uint64_t)(uintptr_t)p->src | (uint64_t)p->stripe_stride | p->cell_bytes |
 			       p->chunk_bytes) & 15u) == 0;
-	uint64_t blocks = (total + CS_WAVES - 1) / CS_WAVES;
 
 	if (total == 0)
 		return (int)hipSuccess;
@@ -892,20 +860,9 @@ extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void 
 	    p->slots > p->k + p->p || p->masks == nullptr || p->chunk_bytes == 0 ||
 	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes)
 		return (int)hipErrorInvalidValue;
-	if (max_blocks == 0)
-		max_blocks = 256 * 16;	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
-	if (blocks > max_blocks)
-		blocks = max_blocks;
-	for (uint32_t i = 0; i < N_MASKED; i++) {
-		if (g_masked[i].type == p->type && g_masked[i].aligned == aligned) {
-			hipLaunchKernelGGL(g_masked[i].fn, dim3((uint32_t)blocks), dim3(CS_BLOCK), 0,
-					   (hipStream_t)stream, *p);
-			if (kernel_id)
-				*kernel_id = KID_MASKED + i;
-			return (int)hipGetLastError();
-		}
-	}
-	return (int)hipErrorInvalidValue;
+	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
+	return launch_row(g_masked, KID_MASKED, aligned, (total + CS_WAVES - 1) / CS_WAVES,
+			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
 }
 
 extern "C" int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
@@ -960,14 +917,9 @@ extern "C" const char *ecg_k_csum_kernel_name(uint32_t id)
 		return "ecg_csum_compare_kernel";
 	if (id == KID_MASK)
 		return "ecg_csum_mask_kernel";
-	if (id >= KID_MASKED && id < KID_MASKED + N_MASKED)
-		return g_masked[id - KID_MASKED].name;
-	if (id >= ECG_KID_CSUM && id < ECG_KID_CSUM + N_CSUM)
-		return g_csum[id - ECG_KID_CSUM].name;
-	if (id >= ECG_KID_CSUM + N_CSUM && id < ECG_KID_CSUM + N_CSUM + N_SPLIT)
-		return g_split[id - ECG_KID_CSUM - N_CSUM].name;
-	if (id >= ECG_KID_CSUM + N_CSUM + N_SPLIT && id < ECG_KID_CSUM + N_CSUM + N_SPLIT + N_GROUP)
-		return g_group[id - ECG_KID_CSUM - N_CSUM - N_SPLIT].name;
+	for (const auto &r : g_ids)
+		if (id >= r.first && id < r.first + r.n)
+			return r.name(id - r.first);
 	return "?";
 }
 
@@ -977,61 +929,25 @@ extern "C" int ecg_k_launch_csum(const ecg_csum_params_t *p, void *stream, uint3
 	const uint64_t total = (uint64_t)p->n_ext * p->nchunks;
 	const bool aligned = (((uint64_t)(uintptr_t)p->src | (uint64_t)p->ext_stride | p->first_bytes |
 			       p->chunk_bytes) & 15u) == 0;
-	uint64_t blocks = (total + CS_WAVES - 1) / CS_WAVES;
+	// a workgroup per chunk when one wave per chunk would leave fewer than 4
+	// waves per SIMD and every wave still gets >= 2 steps (adler32 too:
+	// profiles/r01/bench_csum.json adler32_cs1024K rows)
+	const uint64_t steps = (p->chunk_bytes / 16 + 63) / 64;
+	const bool split = p->variant == 2 || (p->variant == 0 && total < 4096 && steps >= 2 * SPLIT_NW);
 
 	if (total == 0)
 		return (int)hipSuccess;
-	if (aligned) {
-		// a workgroup per chunk when one wave per chunk would leave fewer
-		// than 4 waves per SIMD and every wave still gets >= 2 steps
-		// (adler32 too: profiles/r01/bench_csum.json adler32_cs1024K rows)
-		const uint64_t steps = (p->chunk_bytes / 16 + 63) / 64;
-		const bool split = p->variant == 2 ||
-				   (p->variant == 0 && total < 4096 && steps >= 2 * SPLIT_NW);
-
-		for (uint32_t i = 0; split && i < N_SPLIT; i++) {
-			if (g_split[i].type != p->type || !kind_ok(g_split[i], p))
-				continue;
-			uint64_t nb = total;
-			const uint64_t cap = max_blocks ? max_blocks : 256 * 8;
-
-			if (nb > cap)
-				nb = cap;
-			hipLaunchKernelGGL(g_split[i].fn, dim3((uint32_t)nb), dim3(64 * SPLIT_NW), 0,
-					   (hipStream_t)stream, *p);
-			if (kernel_id)
-				*kernel_id = ECG_KID_CSUM + N_CSUM + i;
-			return (int)hipGetLastError();
-		}
-	}
+	if (aligned && split)
+		return launch_row(g_split, KID_SPLIT, true, total, max_blocks ? max_blocks : 256 * 8, 64 * SPLIT_NW, p,
+				  stream, kernel_id);
 	if (max_blocks == 0)
 		max_blocks = 256 * 16;	// 16 blocks per CU, grid-stride beyond
 	if (p->type != 7 && aligned && p->variant == 3) {
 		const uint32_t per_block = CS_WAVES * (64 / ECG_CSUM_GLANES);
-		uint64_t nb = (total + per_block - 1) / per_block;
 
-		if (nb > max_blocks)
-			nb = max_blocks;
-		for (uint32_t i = 0; i < N_GROUP; i++) {
-			if (g_group[i].type != p->type || !kind_ok(g_group[i], p))
-				continue;
-			hipLaunchKernelGGL(g_group[i].fn, dim3((uint32_t)nb), dim3(CS_BLOCK), 0,
-					   (hipStream_t)stream, *p);
-			if (kernel_id)
-				*kernel_id = ECG_KID_CSUM + N_CSUM + N_SPLIT + i;
-			return (int)hipGetLastError();
-		}
+		return launch_row(g_group, KID_GROUP, true, (total + per_block - 1) / per_block, max_blocks, CS_BLOCK, p,
+				  stream, kernel_id);
 	}
-	if (blocks > max_blocks)
-		blocks = max_blocks;
-	for (uint32_t i = 0; i < N_CSUM; i++) {
-		if (g_csum[i].type == p->type && g_csum[i].aligned == aligned && kind_ok(g_csum[i], p)) {
-			hipLaunchKernelGGL(g_csum[i].fn, dim3((uint32_t)blocks), dim3(CS_BLOCK), 0,
-					   (hipStream_t)stream, *p);
-			if (kernel_id)
-				*kernel_id = ECG_KID_CSUM + i;
-			return (int)hipGetLastError();
-		}
-	}
-	return (int)hipErrorInvalidValue;
+	return launch_row(g_csum, ECG_KID_CSUM, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks, CS_BLOCK, p,
+			  stream, kernel_id);
 }

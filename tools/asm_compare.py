@@ -82,7 +82,8 @@ def nt_blocks(lines):
 def demangle(names):
     try:
         res = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True, check=True)
-        return dict(zip(names, (s.replace("void ", "").split("(")[0] for s in res.stdout.splitlines())))
+        return dict(zip(names, (s.replace("void ", "").replace("(anonymous namespace)::", "").split("(")[0]
+                                     for s in res.stdout.splitlines())))
     except (OSError, subprocess.CalledProcessError):
         return {n: n for n in names}
 
