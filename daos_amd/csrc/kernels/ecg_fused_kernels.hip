@@ -597,8 +597,16 @@ extern "C" int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs
 	const uint64_t ipb = q->ncols == 1 ? 8 : q->ncols == 2 ? 2 : 1;
 	uint32_t gx = cfg && cfg->grid_x ? cfg->grid_x : (uint32_t)((q->nitems + ipb - 1) / ipb);
 	uint32_t gy = cfg && cfg->grid_y ? cfg->grid_y : (p->nstripes < 65535 ? p->nstripes : 65535);
+	// the kernel walks item blockIdx.x of stripe blockIdx.y without a test:
+	// an override (ecg_set_launch) above either count is cut down to it
+	if (gx > q->nitems)
+		gx = q->nitems;
+	if (gy > p->nstripes)
+		gy = p->nstripes;
 	if (gx > 65535)
 		gx = 65535;
+	if (gy > 65535)
+		gy = 65535;
 	hipLaunchKernelGGL(g_cskernels[id].fn, dim3(gx, gy), dim3(BLOCK), 0, (hipStream_t)stream, *p, *q);
 	if (kernel_id)
 		*kernel_id = KID_FUSED + id;

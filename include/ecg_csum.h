@@ -57,8 +57,12 @@ uint32_t ecg_csum_chunk_count(uint64_t chunksize, uint64_t rec_size, uint64_t rx
  * rec_size bytes at buf + e * ext_stride and starts at record index rx_idx
  * (the same index for every extent: chunk boundaries fall on multiples of the
  * record chunk size in index space).  csums: device memory for
- * n_ext * ecg_csum_chunk_count(...) * ecg_csum_len(type) bytes.  Asynchronous
- * on `stream` (NULL = the context stream).  Returns 0 or a negative errno. */
+ * n_ext * ecg_csum_chunk_count(...) * ecg_csum_len(type) bytes, aligned to
+ * ecg_csum_len(type): every checksum is written with one store of its own
+ * width (ecg_csum_masked, below, takes csums at any byte).  buf, ext_stride and
+ * the sizes may be anything; all of them multiples of 16 run the faster
+ * kernels.  Asynchronous on `stream` (NULL = the context stream).  Returns 0
+ * or a negative errno. */
 int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
 		     uint64_t rx_idx, uint64_t rx_nr, const void *buf, int64_t ext_stride,
 		     uint32_t n_ext, void *csums, void *stream);

@@ -270,6 +270,37 @@ def test_encode_csum_fused_items(oracle, ecglib, ctx, case, cols):
         d.free(); par.free(); out.free()
 
 
+@pytest.mark.parametrize("grid", [(64, 0), (0, 64), (64, 64)])
+def test_encode_csum_fused_grid_above_counts(oracle, ecglib, ctx, grid):
+    """An ecg_set_launch grid above the item count (3 chunks of 2 columns: 3 items) or the stripe
+    count (2) is cut down to it: the fused kernel walks its first item without a test.  Parity,
+    checksums and the 0xA5 behind both are the oracle's."""
+    k, p, C, S, cs, htype = 4, 2, 2 * 8192 + 4096 + 48, 2, 8192, 2
+    L = ecglib.lib()
+    nch = L.ecg_csum_chunk_count(cs, 1, 0, C)
+    rng = np.random.default_rng(sum(grid))
+    data = rng.integers(0, 256, S * k * C, dtype=np.uint8)
+    d = ctx.to_device(data)
+    par = ctx.alloc(p * S * C + 4096)
+    out = ctx.alloc(p * S * nch * 4 + 256)
+    try:
+        par.fill(0xA5)
+        out.fill(0xA5)
+        ctx.set_launch(*grid, 0)
+        ctx.encode_csum(k, p, C, S, d.ptr, k * C, par.ptr, S * C, C, htype, cs, 1, out.ptr)
+        ctx.sync()
+        assert L.ecg_last_kernel().decode() == "ecg_mm_csum_kernel<4,2,crc32>"
+        want_par = oracle.encode_batch(k, p, C, S, data, nthreads=8, simd=True)
+        got_par = par.download()
+        assert np.array_equal(got_par[:p * S * C], want_par) and np.all(got_par[p * S * C:] == 0xA5)
+        got = out.download()
+        want = _want_cell_csums(oracle, htype, cs, 1, want_par.reshape(p, S, C)).reshape(-1)
+        assert np.array_equal(got[:p * S * nch * 4].view(np.uint32), want) and np.all(got[p * S * nch * 4:] == 0xA5)
+    finally:
+        ctx.set_launch(0, 0, 0)
+        d.free(); par.free(); out.free()
+
+
 @pytest.mark.parametrize("errs", [[3, 9], [9, 3], [8, 9], [0], [0, 1], [5]])
 @pytest.mark.parametrize("htype", (2, 3))
 def test_recover_csum_fused(oracle, ecglib, ctx, errs, htype):
