@@ -441,6 +441,16 @@ static inline ECG_KABI_HD uint32_t ecg_csum_masked_sel(uint32_t mask, int k, int
  * result[0] += stripes with a valid set, result[1] = min(result[1], lowest
  * stripe whose non-zero mask is no set), result[2] += cells checksummed,
  * result[3] += stripes whose non-zero mask is no set.
+ * cells_dev == NULL: the strided image above.  Otherwise ecg_csum_masked_ptrs:
+ * cell c of stripe s lies at the address cells_dev[s * (k + p) + c] (device
+ * memory, read only for the launch; src and stripe_stride unused); an item
+ * loads its entry after the sel test, so a skipped item reads none.  bytewise
+ * is then the host's lane choice, 0 only when EVERY table entry, cell_bytes and
+ * chunk_bytes are multiples of 16: the launcher does not read the table.
+ * ecg_csum_cells_ptrs (ecg_k_launch_csum_cells) checksums every cell of a
+ * table of ncells entries, item g = chunk g % nch of cell g / nch, out[g] its
+ * checksum; it reads cells_dev, out, tbl, cell_bytes, chunk_bytes, nch, type,
+ * bytewise and the CRC constants.
  */
 typedef struct ecg_csum_masked_params {
 	const uint8_t *src;
@@ -448,17 +458,19 @@ typedef struct ecg_csum_masked_params {
 	const void *tbl;
 	const uint32_t *masks;
 	uint64_t *result;
+	const uint64_t *cells_dev;
 	int64_t stripe_stride;
 	uint64_t cell_bytes;
 	uint64_t chunk_bytes;
 	uint64_t init, xorout, poly;
+	uint64_t ncells;
 	uint32_t nstripes;
 	uint32_t nch;
 	uint32_t k, p;
 	uint32_t which;
 	uint32_t slots;
 	uint32_t type;
-	uint32_t pad;
+	uint32_t bytewise;
 } ecg_csum_masked_params_t;
 
 /*
@@ -561,9 +573,13 @@ const char *ecg_k_update_masks_kernel_name(uint32_t kernel_id);
 int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
 			   uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride, uint32_t first_cell,
 			   uint32_t len, uint32_t *masks, void *stream, uint32_t *kernel_id);
-/* ecg_csum_masked (kernels/ecg_csum_kernels.hip); max_blocks 0 = default. */
+/* ecg_csum_masked and, with p->cells_dev, ecg_csum_masked_ptrs (kernels/
+ * ecg_csum_kernels.hip); max_blocks 0 = default. */
 int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
 			     uint32_t *kernel_id);
+/* ecg_csum_cells_ptrs: every cell of the table p->cells_dev (p->ncells entries). */
+int ecg_k_launch_csum_cells(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
+			    uint32_t *kernel_id);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of

@@ -797,11 +797,13 @@ struct masked_geom {
 };
 
 /* Argument checks of ecg_csum_masked for the array `csums` (`what` names it),
- * everything but the context; result == NULL is accepted with need_result = 0. */
+ * everything but the context; result == NULL is accepted with need_result = 0.
+ * table: the checks of a cell-table call that come before its context check --
+ * no stripes; what csums must not overlap is checked entry by entry later. */
 static int masked_check(const char *fn, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
-			uint32_t S, const void *stripes, int64_t stripe_stride, const uint32_t *masks, unsigned which,
-			const void *csums, const char *what, const void *result, int need_result, unsigned flags,
-			struct masked_geom *g)
+			uint32_t S, int table, const void *stripes, int64_t stripe_stride, const uint32_t *masks,
+			unsigned which, const void *csums, const char *what, const void *result, int need_result,
+			unsigned flags, struct masked_geom *g)
 {
 	const int cl = ecg_csum_len(type);
 	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
@@ -830,32 +832,45 @@ static int masked_check(const char *fn, int type, uint64_t chunksize, uint64_t r
 	nch = C / rcs + (C % rcs != 0);
 	if (nch > UINT32_MAX || __builtin_mul_overflow(nch * (uint64_t)(k + p), (uint64_t)cl * S, &bytes))
 		return ecg_fail(-ECG_DER_INVAL, "%s: too many checksums", fn);
+	g->rcs = rcs;
+	g->bytes = bytes;
+	g->nch = (uint32_t)nch;
+	if (table) {
+		if (S && C && csums == NULL)
+			return ecg_fail(-ECG_DER_INVAL, "%s: NULL %s", fn, what);
+		return 0;
+	}
 	if (S && C && (stripes == NULL || csums == NULL))
 		return ecg_fail(-ECG_DER_INVAL, "%s: NULL stripes or %s", fn, what);
 	if (S && C && ecg_cells_overlap(csums, bytes, stripes, S, stripe_stride, k + p, (int64_t)C, C))
 		return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps the stripes", fn, what);
 	if (C && ranges_overlap(csums, bytes, masks, 4ull * S))
 		return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps the masks", fn, what);
-	g->rcs = rcs;
-	g->bytes = bytes;
-	g->nch = (uint32_t)nch;
 	return 0;
 }
 
-/* One ecg_csum_masked launch on st; result NULL = nothing counted. */
-static int masked_launch(ecg_ctx_t *ctx, int type, const struct masked_geom *g, int k, int p, uint64_t C, uint32_t S,
-			 const void *stripes, int64_t stripe_stride, const uint32_t *masks, unsigned which,
-			 void *csums, void *result, hipStream_t st)
+/* The CRC tables of a hash type (NULL for adler32, which has none).  Takes
+ * ctx->lock: fetched before a cell-table call locks its scratch slot. */
+static int masked_tbl(ecg_ctx_t *ctx, int type, const void **tbl)
+{
+	*tbl = NULL;
+	return type == ECG_HASH_ADLER32 ? 0 : crc_tables(ctx, type, tbl);
+}
+
+/* One ecg_csum_masked launch on st; result NULL = nothing counted.  Over the
+ * strided image `stripes`, or with cells_dev over a staged cell table (bytewise:
+ * an entry, C or the chunk size is no multiple of 16). */
+static int masked_launch(ecg_ctx_t *ctx, int type, const void *tbl, const struct masked_geom *g, int k, int p,
+			 uint64_t C, uint32_t S, const void *stripes, int64_t stripe_stride, const uint64_t *cells_dev,
+			 int bytewise, const uint32_t *masks, unsigned which, void *csums, void *result, hipStream_t st)
 {
 	ecg_csum_masked_params_t prm;
 	uint32_t kid = 0;
-	int rc, e;
+	int e;
 
 	memset(&prm, 0, sizeof(prm));
 	if (type != ECG_HASH_ADLER32) {
-		rc = crc_tables(ctx, type, &prm.tbl);
-		if (rc)
-			return rc;
+		prm.tbl = tbl;
 		prm.poly = g_defs[type].poly;
 		prm.init = g_defs[type].init;
 		prm.xorout = g_defs[type].xorout;
@@ -864,6 +879,8 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const struct masked_geom *g, 
 	prm.out = csums;
 	prm.masks = masks;
 	prm.result = result;
+	prm.cells_dev = cells_dev;
+	prm.bytewise = (uint32_t)bytewise;
 	prm.stripe_stride = stripe_stride;
 	prm.cell_bytes = C;
 	prm.chunk_bytes = g->rcs;
@@ -874,9 +891,10 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const struct masked_geom *g, 
 	prm.which = which;
 	prm.slots = (which & ECG_CM_ERASED ? (uint32_t)p : 0) + (which & ECG_CM_SURVIVORS ? (uint32_t)k : 0);
 	prm.type = (uint32_t)type;
-	ecg_trace_push("ecg:csum_masked");
+	ecg_trace_push(cells_dev ? "ecg:csum_masked_ptrs" : "ecg:csum_masked");
 	e = ecg_k_launch_csum_masked(&prm, (void *)st, ctx->csum_blocks, &kid);
-	return ecg_launch_done(ctx, e, "csum_masked kernel launch", 1, ecg_k_kernel_name(kid));
+	return ecg_launch_done(ctx, e, cells_dev ? "csum_masked_ptrs kernel launch" : "csum_masked kernel launch", 1,
+			       ecg_k_kernel_name(kid));
 }
 
 /* ECG_RM_SPARSE is accepted and ignored: the one grid serves dense and clean
@@ -886,10 +904,11 @@ int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_s
 		    unsigned which, void *csums, void *result, unsigned flags, void *stream)
 {
 	struct masked_geom g;
+	const void *tbl;
 	hipStream_t st;
 	int rc;
 
-	rc = masked_check("csum_masked", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride, masks, which,
+	rc = masked_check("csum_masked", type, chunksize, rec_size, k, p, C, S, 0, stripes, stripe_stride, masks, which,
 			  csums, "csums", result, 1, flags, &g);
 	if (rc)
 		return rc;
@@ -905,7 +924,11 @@ int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_s
 		return rc;
 	if (S == 0 || C == 0)
 		return 0;
-	return masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks, which, csums, result, st);
+	rc = masked_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	return masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks, which, csums,
+			     result, st);
 }
 
 int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *stripes,
@@ -914,6 +937,7 @@ int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 {
 	const int one = src_csums != NULL && src_csums == csums;	/* one array, one which = 3 launch */
 	struct masked_geom g;
+	const void *tbl;
 	hipStream_t st;
 	int rc;
 
@@ -921,12 +945,12 @@ int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	rc = ecg_recover_masks_check("recover_masks_csum", 1, k, p, C, S, stripes, stripe_stride, masks, result, flags);
 	if (rc)
 		return rc;
-	rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride, masks,
+	rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, 0, stripes, stripe_stride, masks,
 			  one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, "csums", NULL, 0, flags, &g);
 	if (rc)
 		return rc;
 	if (src_csums != NULL && !one) {
-		rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, stripes, stripe_stride,
+		rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, 0, stripes, stripe_stride,
 				  masks, ECG_CM_SURVIVORS, src_csums, "src_csums", NULL, 0, flags, &g);
 		if (rc)
 			return rc;
@@ -940,11 +964,257 @@ int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (rc || S == 0 || C == 0)
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
-	rc = masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks,
+	rc = masked_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks,
 			   one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, NULL, st);
 	if (rc == 0 && src_csums != NULL && !one)
-		rc = masked_launch(ctx, type, &g, k, p, C, S, stripes, stripe_stride, masks, ECG_CM_SURVIVORS,
-				   src_csums, NULL, st);
+		rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks,
+				   ECG_CM_SURVIVORS, src_csums, NULL, st);
+	return rc;
+}
+
+/*
+ * The cell-table forms.  Each stages the caller's table as
+ * ecg_recover_masks_ptrs stages its own (ecg_recover_masks.c): a scratch slot
+ * reserved under ctx->lock, one pass of ecg_cell_table into its pinned half,
+ * ecg_table_upload, the launches, and ecg_table_done.  Whatever takes ctx->lock
+ * itself (the CRC tables, the set table) is fetched before.
+ */
+
+int ecg_csum_masked_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
+			 uint32_t S, void *const *cells, const uint32_t *masks, unsigned which, void *csums,
+			 void *result, unsigned flags, void *stream)
+{
+	struct ecg_scratch_slot *sc = NULL;
+	struct masked_geom g;
+	const void *tbl;
+	uint64_t bits = 0;
+	int64_t stride = 0;
+	size_t tbytes;
+	hipStream_t st;
+	uint32_t n;
+	int rc, affine = 0;
+
+	rc = masked_check("csum_masked_ptrs", type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, which, csums,
+			  "csums", result, 1, flags, &g);
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: NULL context");
+	if (S && C && cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: NULL cells");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* result = {0, UINT64_MAX, 0, 0} and nothing else */
+		return ecg_result_reset(result, st, "csum_masked_ptrs memset");
+	rc = masked_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	n = (uint32_t)(k + p);
+	tbytes = (size_t)S * n * sizeof(uint64_t);
+
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	if (rc == 0) {
+		const struct ecg_clear clear[3] = {
+			{csums, g.bytes, "csums"}, {masks, 4ull * S, "masks"}, {result, 32, "result"}};
+
+		rc = ecg_cell_table("csum_masked_ptrs", sc->pin, cells, S, n, C, clear, 3, &bits, &affine, &stride);
+	}
+	if (rc == 0 && ranges_overlap(csums, g.bytes, masks, 4ull * S))
+		rc = ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: csums overlaps the masks");
+	/* ecg_csum_masked's own layout, and csums clear of the whole image as it
+	 * demands: its launch, with no table */
+	if (rc == 0 && affine && !ecg_cells_overlap(csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C)) {
+		pthread_mutex_unlock(&ctx->lock);
+		return ecg_csum_masked(ctx, type, chunksize, rec_size, k, p, C, S, cells[0], stride, masks, which, csums,
+				       result, flags, stream);
+	}
+	if (rc == 0)
+		rc = ecg_result_reset(result, st, "csum_masked_ptrs memset");
+	if (rc == 0)
+		rc = ecg_table_upload(sc, tbytes, st, "csum_masked_ptrs cell table");
+	if (rc == 0) {
+		rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0, masks,
+				   which, csums, result, st);
+		rc = ecg_table_done(sc, st, rc);
+	}
+	pthread_mutex_unlock(&ctx->lock);
+	return rc;
+}
+
+int ecg_csum_cells_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, uint64_t C, uint64_t ncells,
+			void *const *cells, void *csums, void *stream)
+{
+	const int cl = ecg_csum_len(type);
+	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
+	struct ecg_scratch_slot *sc = NULL;
+	ecg_csum_masked_params_t prm;
+	uint64_t nch, bytes, bits = 0;
+	int64_t stride = 0;
+	uint32_t kid = 0;
+	hipStream_t st;
+	size_t tbytes;
+	int rc, e, affine = 0;
+
+	if (cl < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "csum_cells_ptrs: hash type %d not supported", type);
+	if (rcs == 0)
+		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: chunksize and rec_size must not be 0");
+	if (C % rec_size)
+		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: cell_bytes %llu is not a multiple of rec_size %llu",
+				(unsigned long long)C, (unsigned long long)rec_size);
+	nch = C / rcs + (C % rcs != 0);
+	if (nch > UINT32_MAX || __builtin_mul_overflow(nch * (uint64_t)cl, ncells, &bytes) ||
+	    ncells > SIZE_MAX / sizeof(uint64_t))
+		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: too many checksums");
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: NULL context");
+	if (ncells && C && (cells == NULL || csums == NULL))
+		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: NULL cells or csums");
+	rc = ecg_ctx_enter(ctx);
+	if (rc || ncells == 0 || C == 0)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	memset(&prm, 0, sizeof(prm));
+	rc = masked_tbl(ctx, type, &prm.tbl);
+	if (rc)
+		return rc;
+	if (type != ECG_HASH_ADLER32) {
+		prm.poly = g_defs[type].poly;
+		prm.init = g_defs[type].init;
+		prm.xorout = g_defs[type].xorout;
+	}
+	tbytes = (size_t)ncells * sizeof(uint64_t);
+
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	if (rc == 0) {
+		const struct ecg_clear clear = {csums, bytes, "csums"};
+
+		/* a table of ncells rows of one cell; no affine route: ecg_csum_extents
+		 * wants csums aligned and picks its kernels by shape */
+		rc = ecg_cell_table("csum_cells_ptrs", sc->pin, cells, ncells, 1, C, &clear, 1, &bits, &affine, &stride);
+	}
+	if (rc == 0)
+		rc = ecg_table_upload(sc, tbytes, st, "csum_cells_ptrs cell table");
+	if (rc == 0) {
+		prm.out = csums;
+		prm.cells_dev = sc->dev;
+		prm.bytewise = (bits | C | rcs) % 16u != 0;
+		prm.cell_bytes = C;
+		prm.chunk_bytes = rcs;
+		prm.ncells = ncells;
+		prm.nch = (uint32_t)nch;
+		prm.type = (uint32_t)type;
+		ecg_trace_push("ecg:csum_cells_ptrs");
+		e = ecg_k_launch_csum_cells(&prm, (void *)st, ctx->csum_blocks, &kid);
+		rc = ecg_launch_done(ctx, e, "csum_cells_ptrs kernel launch", 1, ecg_k_kernel_name(kid));
+		rc = ecg_table_done(sc, st, rc);
+	}
+	pthread_mutex_unlock(&ctx->lock);
+	if (rc == 0)
+		ECG_STAT_ADD(ctx, csum_chunks, ncells * nch);
+	return rc;
+}
+
+int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+				const uint32_t *masks, void *result, unsigned flags, int type, uint64_t chunksize,
+				uint64_t rec_size, void *csums, void *src_csums, void *stream)
+{
+	static const char fn[] = "recover_masks_ptrs_csum";
+	const int one = src_csums != NULL && src_csums == csums;	/* one array, one which = 3 launch */
+	const int two = src_csums != NULL && !one;
+	const unsigned first = one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED;
+	struct ecg_scratch_slot *sc = NULL;
+	const void *settbl = NULL, *tbl;
+	struct masked_geom g;
+	uint64_t bits = 0;
+	int64_t stride = 0;
+	size_t tbytes;
+	hipStream_t st;
+	uint32_t n;
+	int rc, affine = 0;
+
+	/* both halves' argument errors before anything is queued (no stripes: the
+	 * cells are checked entry by entry below) */
+	rc = ecg_recover_masks_check(fn, 1, k, p, 0, S, NULL, 0, masks, result, flags);
+	if (rc)
+		return rc;
+	rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, first, csums, "csums", NULL, 0,
+			  flags, &g);
+	if (rc)
+		return rc;
+	if (two) {
+		rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, ECG_CM_SURVIVORS,
+				  src_csums, "src_csums", NULL, 0, flags, &g);
+		if (rc)
+			return rc;
+		if (S && C && ranges_overlap(csums, g.bytes, src_csums, g.bytes))
+			return ecg_fail(-ECG_DER_INVAL, "%s: src_csums must be csums itself or not overlap it", fn);
+	}
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	if (S && C && cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells", fn);
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing recovered, nothing left */
+		return ecg_result_reset(result, st, "recover_masks_ptrs_csum memset");
+	rc = ecg_rm_settbl(ctx, k, p, &settbl);
+	if (rc == 0)
+		rc = masked_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	n = (uint32_t)(k + p);
+	tbytes = (size_t)S * n * sizeof(uint64_t);
+
+	/* the table is checked and staged once for the two or three launches */
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	if (rc == 0) {
+		const struct ecg_clear clear[4] = {{masks, 4ull * S, "masks"}, {result, 32, "result"},
+						   {csums, g.bytes, "csums"},
+						   {src_csums, two ? g.bytes : 0, "src_csums"}};
+
+		rc = ecg_cell_table(fn, sc->pin, cells, S, n, C, clear, 4, &bits, &affine, &stride);
+	}
+	if (rc == 0 && ranges_overlap(csums, g.bytes, masks, 4ull * S))
+		rc = ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the masks", fn);
+	if (rc == 0 && two && ranges_overlap(src_csums, g.bytes, masks, 4ull * S))
+		rc = ecg_fail(-ECG_DER_INVAL, "%s: src_csums overlaps the masks", fn);
+	/* the layout of ecg_recover_masks_csum, and masks and the checksum arrays
+	 * clear of the whole image as it demands: that call, with no table */
+	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C) &&
+	    !ecg_cells_overlap(csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C) &&
+	    !(two && ecg_cells_overlap(src_csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C))) {
+		pthread_mutex_unlock(&ctx->lock);
+		return ecg_recover_masks_csum(ctx, k, p, C, S, cells[0], stride, masks, result, flags, type, chunksize,
+					      rec_size, csums, src_csums, stream);
+	}
+	if (rc == 0)
+		rc = ecg_result_reset(result, st, "recover_masks_ptrs_csum memset");
+	if (rc == 0)
+		rc = ecg_table_upload(sc, tbytes, st, "recover_masks_ptrs_csum cell table");
+	if (rc == 0) {
+		rc = ecg_rm_launch(ctx, fn, settbl, k, p, C, S, NULL, 0, sc->dev, (bits | C) % 16u != 0, masks, result,
+				   flags, st);
+		if (rc == 0)
+			rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0,
+					   masks, first, csums, NULL, st);
+		if (rc == 0 && two)
+			rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0,
+					   masks, ECG_CM_SURVIVORS, src_csums, NULL, st);
+		/* the fetch and every kernel above read the slot: the next user waits */
+		rc = ecg_table_done(sc, st, rc);
+	}
+	pthread_mutex_unlock(&ctx->lock);
 	return rc;
 }
 

@@ -133,6 +133,10 @@ int ecg_scratch_reserve(ecg_ctx_t *ctx, size_t pin_bytes, size_t dev_bytes,
 /* The first `bytes` of sc->pin to sc->dev, queued on st (a fetch kernel:
  * ecg_k_launch_fetch); `what` names the table in the error. */
 int ecg_table_upload(struct ecg_scratch_slot *sc, size_t bytes, hipStream_t st, const char *what);
+/* After the last launch queued on st that reads the slot (rc: how the launches
+ * went): its `done` event, for which the slot's next user waits (ctx->lock
+ * held).  Returns rc, or the event's failure when rc was 0. */
+int ecg_table_done(struct ecg_scratch_slot *sc, hipStream_t st, int rc);
 
 /* batched segment copies (ecg_sgl.c).  A fixed list (cap preset, fixed = 1)
  * writes into caller memory and fails instead of growing. */
@@ -169,6 +173,28 @@ void ecg_ctx_kp_tables_fini(void **slots, int nk, int np);	/* frees nk x np of t
  * the message; have_ctx = 0 fails where it reports a NULL context) */
 int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t C, uint32_t S, const void *stripes,
 			    int64_t stripe_stride, const uint32_t *masks, const void *result, unsigned flags);
+/* what the cell-table calls share (ecg_recover_masks.c): ecg_recover_masks_ptrs
+ * and, in ecg_csum.c, ecg_csum_masked_ptrs, ecg_csum_cells_ptrs and
+ * ecg_recover_masks_ptrs_csum */
+/* a range no cell of a table may share a byte with; `what` names it in the error */
+struct ecg_clear {
+	const void *at;
+	uint64_t len;
+	const char *what;
+};
+/* One pass over the caller's table of S x n addresses of cells of C bytes into
+ * tab (the pinned half of a scratch slot): -ECG_DER_INVAL for a NULL entry or
+ * a `clear` range inside a cell, naming `fn` and the entry; *bits = the OR of
+ * the addresses, *affine = the table is cells[0] + s * *stride + c * C. */
+int ecg_cell_table(const char *fn, uint64_t *tab, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
+		   const struct ecg_clear *clear, int nclear, uint64_t *bits, int *affine, int64_t *stride);
+/* the set table of (k, p), built on first use; takes ctx->lock */
+int ecg_rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl);
+/* the recover_masks launch over the strided image `stripes`, or with cells_dev
+ * over a staged cell table (stripes NULL); fn names the call */
+int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int p, uint64_t C, uint32_t S,
+		  void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
+		  const uint32_t *masks, void *result, unsigned flags, hipStream_t st);
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);

@@ -99,6 +99,17 @@ int ecg_table_upload(struct ecg_scratch_slot *sc, size_t bytes, hipStream_t st, 
 	return e == hipSuccess ? 0 : ecg_hip_fail(e, what);
 }
 
+int ecg_table_done(struct ecg_scratch_slot *sc, hipStream_t st, int rc)
+{
+	const hipError_t he = hipEventRecord(sc->done, st);
+
+	if (he == hipSuccess)
+		sc->pending = 1;
+	else if (rc == 0)
+		rc = ecg_hip_fail(he, "scratch event record");
+	return rc;
+}
+
 void ecg_scratch_free(ecg_ctx_t *ctx)
 {
 	for (int i = 0; i < ECG_NSCRATCH; i++) {

@@ -23,6 +23,11 @@
  * as ecg_matmul_ptrs stages its own (ecg_ptrs.c), and the cell-table kernels
  * of the same file.  A table that is a strided image after all is handed to
  * ecg_recover_masks.
+ *
+ * The pass over such a table (ecg_cell_table), the set table's fetch and the
+ * launch are shared with the cell-table checksum calls of ecg_csum.c, which
+ * stage the same table (ecg_csum_masked_ptrs, ecg_csum_cells_ptrs) and run this
+ * launch in front of theirs (ecg_recover_masks_ptrs_csum).
  */
 #include <stdlib.h>
 #include <string.h>
@@ -140,7 +145,7 @@ int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t
 
 /* The set table of (k, p), one per context: synchronous on first use.  Takes
  * ctx->lock, so it is fetched before ecg_recover_masks_ptrs locks its slot. */
-static int rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl)
+int ecg_rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl)
 {
 	const int kp[2] = {k, p};
 
@@ -152,9 +157,9 @@ static int rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl)
 /* The launch of both calls (fn names the call in the trace range and the
  * messages): over the strided image `stripes`, or with cells_dev over the
  * staged cell table (stripes NULL). */
-static int rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int p, uint64_t C, uint32_t S,
-		     void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
-		     const uint32_t *masks, void *result, unsigned flags, hipStream_t st)
+int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int p, uint64_t C, uint32_t S,
+		  void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
+		  const uint32_t *masks, void *result, unsigned flags, hipStream_t st)
 {
 	const int ptrs = cells_dev != NULL;
 	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
@@ -202,41 +207,41 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	rc = ecg_result_reset(result, st, "recover_masks memset");
 	if (rc || S == 0 || C == 0)
 		return rc;
-	rc = rm_settbl(ctx, k, p, &settbl);
+	rc = ecg_rm_settbl(ctx, k, p, &settbl);
 	if (rc)
 		return rc;
-	return rm_launch(ctx, "recover_masks", settbl, k, p, C, S, stripes, stripe_stride, NULL,
-			 ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u != 0, masks, result, flags, st);
+	return ecg_rm_launch(ctx, "recover_masks", settbl, k, p, C, S, stripes, stripe_stride, NULL,
+			     ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u != 0, masks, result, flags, st);
 }
 
-/* One pass over the caller's table of S x n cell addresses, copying it into
- * `tab` (the pinned half of a scratch slot): a NULL entry and masks or result
- * inside a cell fail; *bits = the OR of the addresses (the lane choice);
- * *affine = every entry is cells[0] + s * *stride + c * C, the layout of
- * ecg_recover_masks (S == 1: any stride). */
-static int rmp_table(uint64_t *tab, void *const *cells, uint32_t S, uint32_t n, uint64_t C, const uint32_t *masks,
-		     const void *result, uint64_t *bits, int *affine, int64_t *stride)
+/* One pass over a caller's table of S x n cell addresses for the call `fn`,
+ * copying it into `tab` (the pinned half of a scratch slot): a NULL entry fails,
+ * and so does any of the nclear ranges `clear` sharing a byte with a cell of C
+ * bytes (an empty range shares none); *bits = the OR of the addresses (the lane
+ * choice); *affine = every entry is cells[0] + s * *stride + c * C, the layout
+ * of a strided image (S == 1: any stride). */
+int ecg_cell_table(const char *fn, uint64_t *tab, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
+		   const struct ecg_clear *clear, int nclear, uint64_t *bits, int *affine, int64_t *stride)
 {
-	const uint64_t m0 = (uint64_t)(uintptr_t)masks, m1 = m0 + 4ull * S;
-	const uint64_t r0 = (uint64_t)(uintptr_t)result, r1 = r0 + 32u;
 	const uint64_t c0 = (uint64_t)(uintptr_t)cells[0];
 	const uint64_t st = S > 1 ? (uint64_t)(uintptr_t)cells[n] - c0 : (uint64_t)n * C;
 	uint64_t all = 0;
 	int aff = 1;
 
-	for (uint32_t s = 0; s < S; s++)
+	for (uint64_t s = 0; s < S; s++)
 		for (uint32_t c = 0; c < n; c++) {
-			const size_t i = (size_t)s * n + c;
+			const size_t i = (size_t)(s * n + c);
 			const uint64_t a = (uint64_t)(uintptr_t)cells[i];
 
 			if (a == 0)
-				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: NULL cell %zu", i);
-			/* the kernel reads mask words and counts into result while
-			 * other blocks write cells */
-			if (m0 < a + C && a < m1)
-				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: masks overlaps cell %zu", i);
-			if (r0 < a + C && a < r1)
-				return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: result overlaps cell %zu", i);
+				return ecg_fail(-ECG_DER_INVAL, "%s: NULL cell %zu", fn, i);
+			for (int r = 0; r < nclear; r++) {
+				const uint64_t r0 = (uint64_t)(uintptr_t)clear[r].at;
+
+				if (clear[r].len && r0 < a + C && a < r0 + clear[r].len)
+					return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps cell %zu", fn, clear[r].what,
+							i);
+			}
 			tab[i] = a;
 			all |= a;
 			aff &= a == c0 + s * st + c * C;
@@ -273,7 +278,7 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (S == 0 || C == 0)	/* nothing recovered, nothing left */
 		return ecg_result_reset(result, st, "recover_masks_ptrs memset");
 
-	rc = rm_settbl(ctx, k, p, &settbl);	/* ecg_recover_masks's */
+	rc = ecg_rm_settbl(ctx, k, p, &settbl);	/* ecg_recover_masks's */
 	if (rc)
 		return rc;
 
@@ -281,8 +286,13 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	 * array is free again when this returns */
 	pthread_mutex_lock(&ctx->lock);
 	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
-	if (rc == 0)
-		rc = rmp_table(sc->pin, cells, S, n, C, masks, result, &bits, &affine, &stride);
+	if (rc == 0) {
+		/* the kernel reads mask words and counts into result while other
+		 * blocks write cells */
+		const struct ecg_clear clear[2] = {{masks, 4ull * S, "masks"}, {result, 32, "result"}};
+
+		rc = ecg_cell_table("recover_masks_ptrs", sc->pin, cells, S, n, C, clear, 2, &bits, &affine, &stride);
+	}
 	/* ecg_recover_masks's own layout (and masks clear of the whole image, as
 	 * it demands): its launch, with no table and no dependent address loads */
 	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C)) {
@@ -294,16 +304,10 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (rc == 0)
 		rc = ecg_table_upload(sc, tbytes, st, "recover_masks_ptrs cell table");
 	if (rc == 0) {
-		hipError_t he;
-
-		rc = rm_launch(ctx, "recover_masks_ptrs", settbl, k, p, C, S, NULL, 0, sc->dev, (bits | C) % 16u != 0,
-			       masks, result, flags, st);
+		rc = ecg_rm_launch(ctx, "recover_masks_ptrs", settbl, k, p, C, S, NULL, 0, sc->dev,
+				   (bits | C) % 16u != 0, masks, result, flags, st);
 		/* the fetch (and the kernel) read the slot: the next user waits */
-		he = hipEventRecord(sc->done, st);
-		if (he == hipSuccess)
-			sc->pending = 1;
-		else if (rc == 0)
-			rc = ecg_hip_fail(he, "scratch event record");
+		rc = ecg_table_done(sc, st, rc);
 	}
 	pthread_mutex_unlock(&ctx->lock);
 	return rc;

@@ -26,8 +26,9 @@
 // blocks stride over chunks so each block loads them once.
 //
 // Each kernel family is built from one body.  The wave-per-item kernels of
-// extents and of masked cells are crc_wave / adler_wave over an addressing
-// struct (cs_extents, cs_masked); the group and split kernels keep their own
+// extents, of masked cells and of cell tables are crc_wave / adler_wave over an
+// addressing struct (cs_extents, cs_masked<PTRS>, cs_cells); the group and split
+// kernels keep their own
 // loops and take the CRC prologue and finish (crc_lane) and the adler32 sums
 // (adler_lane, adler_wave_sum, adler_finish) from the same helpers.
 #include <hip/hip_runtime.h>
@@ -262,6 +263,32 @@ struct cs_extents {
 	}
 };
 
+// A checksum of LEN bytes, little-endian, at byte `at` of an array that may lie
+// at any byte; a crc16 slot is two bytes wide, so its neighbours may belong to
+// cells that are not selected.
+template <int LEN, typename T>
+__device__ __forceinline__ void store_at(uint8_t *at, T v)
+{
+	if (((uintptr_t)at & (LEN - 1)) == 0) {
+		if constexpr (LEN == 2)
+			*(uint16_t *)at = (uint16_t)v;
+		else
+			*(T *)at = v;
+	} else {
+#pragma unroll
+		for (int b = 0; b < LEN; b++)
+			at[b] = (uint8_t)(v >> (8 * b));
+	}
+}
+
+// Entry i of a cell table, i wave-uniform: the table is read only for the launch
+// (an earlier launch on the stream wrote it), so the load may go through the
+// constant address space, where a uniform index makes it one scalar load.
+__device__ __forceinline__ const uint8_t *table_cell(const uint64_t *tab, uint64_t i)
+{
+	return (const uint8_t *)(uintptr_t)((const __attribute__((address_space(4))) uint64_t *)tab)[i];
+}
+
 // ecg_csum_masked: the checksums of the cells each stripe's mask word selects
 // (ecg_kabi.h ecg_csum_masked_sel), a wave per (stripe, selected cell, chunk).
 // Item g = (s * slots + r) * nch + c reads masks[s] (wave-uniform), takes the
@@ -270,6 +297,11 @@ struct cs_extents {
 // stripe into result.  Every address derives from sel, which is 0 unless
 // ecg_erasure_set_read reads the word as a set and has no bit at or above
 // k + p: all 2^32 mask values are safe.
+// PTRS (ecg_csum_masked_ptrs): the cell's address is the entry s * (k + p) +
+// cell of the table p.cells_dev -- one wave-uniform 8-byte load per item, after
+// the sel test, so a skipped item reads no entry and a stripe whose mask is no
+// set reads none at all.
+template <bool PTRS>
 struct cs_masked {
 	using params = ecg_csum_masked_params_t;
 
@@ -321,27 +353,56 @@ struct cs_masked {
 		const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
 
 		len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
-		base = p.src + (int64_t)s * p.stripe_stride + (uint64_t)cell * p.cell_bytes + off;
+		if constexpr (PTRS)
+			// (cell comes from a vector load of masks[s]: uniform, but the
+			// compiler cannot know)
+			base = table_cell(p.cells_dev, s * (p.k + p.p) + __builtin_amdgcn_readfirstlane(cell)) + off;
+		else
+			base = p.src + (int64_t)s * p.stripe_stride + (uint64_t)cell * p.cell_bytes + off;
 		slot = (s * (p.k + p.p) + cell) * p.nch + c;
 		return true;
 	}
-	// little-endian; the array may lie at any byte, and a crc16 slot is two
-	// bytes wide: its neighbours may belong to cells that are not selected
 	template <int LEN, typename T>
 	static __device__ __forceinline__ void store(const params &p, uint64_t slot, T v)
 	{
-		uint8_t *at = p.out + slot * LEN;
+		store_at<LEN>(p.out + slot * LEN, v);
+	}
+};
 
-		if (((uintptr_t)at & (LEN - 1)) == 0) {
-			if constexpr (LEN == 2)
-				*(uint16_t *)at = (uint16_t)v;
-			else
-				*(T *)at = v;
+// ecg_csum_cells_ptrs: every chunk of every cell of a table, item g = chunk
+// g % nch of the cell at cells_dev[g / nch] (a wave-uniform load); the checksums
+// are an array indexed by g that may lie at any byte.
+struct cs_cells {
+	using params = ecg_csum_masked_params_t;
+
+	static __device__ __forceinline__ uint64_t total(const params &p) { return p.ncells * p.nch; }
+	static __device__ __forceinline__ uint32_t wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+	static __device__ __forceinline__ bool item(const params &p, uint64_t g, const uint8_t *&base, uint64_t &len,
+						    uint64_t &slot)
+	{
+		uint64_t i;
+		uint32_t c;
+
+		if ((g >> 32) == 0) {	// as chunk_geom_fast
+			const uint32_t i32 = (uint32_t)g / p.nch;
+
+			i = i32;
+			c = (uint32_t)g - i32 * p.nch;
 		} else {
-#pragma unroll
-			for (int b = 0; b < LEN; b++)
-				at[b] = (uint8_t)(v >> (8 * b));
+			i = g / p.nch;
+			c = (uint32_t)(g - i * p.nch);
 		}
+		const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
+
+		len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
+		base = table_cell(p.cells_dev, i) + off;
+		slot = g;
+		return true;
+	}
+	template <int LEN, typename T>
+	static __device__ __forceinline__ void store(const params &p, uint64_t slot, T v)
+	{
+		store_at<LEN>(p.out + slot * LEN, v);
 	}
 };
 
@@ -401,7 +462,19 @@ __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_kernel(ecg_csum_params_t p)
 template <int W, bool REFL, bool ALIGNED, int TK>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_kernel(ecg_csum_masked_params_t p)
 {
-	crc_wave<W, REFL, ALIGNED, TK, cs_masked>(p);
+	crc_wave<W, REFL, ALIGNED, TK, cs_masked<false>>(p);
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_ptr_kernel(ecg_csum_masked_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_masked<true>>(p);
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_cells_ptr_kernel(ecg_csum_masked_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_cells>(p);
 }
 
 template <typename T>
@@ -643,7 +716,19 @@ __global__ __launch_bounds__(CS_BLOCK) void ecg_adler_kernel(ecg_csum_params_t p
 template <bool ALIGNED>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_kernel(ecg_csum_masked_params_t p)
 {
-	adler_wave<ALIGNED, cs_masked>(p);
+	adler_wave<ALIGNED, cs_masked<false>>(p);
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_ptr_kernel(ecg_csum_masked_params_t p)
+{
+	adler_wave<ALIGNED, cs_masked<true>>(p);
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_cells_ptr_kernel(ecg_csum_masked_params_t p)
+{
+	adler_wave<ALIGNED, cs_cells>(p);
 }
 
 // adler32 of long chunks that are few (one wave per chunk would leave the
@@ -800,6 +885,29 @@ const csum_entry<ecg_csum_masked_params_t> g_masked[] = {
 	{7, false, ecg_adler_masked_kernel<false>, "ecg_adler_masked_kernel<bytes>"},
 };
 
+// the cell-table kernels of ecg_csum_masked_ptrs and ecg_csum_cells_ptrs
+const csum_entry<ecg_csum_masked_params_t> g_masked_ptr[] = {
+	{1, true, ecg_crc_masked_ptr_kernel<16, false, true, TK_4>, "ecg_crc_masked_ptr_kernel<crc16>"},
+	{1, false, ecg_crc_masked_ptr_kernel<16, false, false, TK_5>, "ecg_crc_masked_ptr_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_masked_ptr_kernel<32, true, true, TK_4>, "ecg_crc_masked_ptr_kernel<crc32>"},
+	{2, false, ecg_crc_masked_ptr_kernel<32, true, false, TK_5>, "ecg_crc_masked_ptr_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_masked_ptr_kernel<64, true, true, TK_4>, "ecg_crc_masked_ptr_kernel<crc64>"},
+	{3, false, ecg_crc_masked_ptr_kernel<64, true, false, TK_5>, "ecg_crc_masked_ptr_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_masked_ptr_kernel<true>, "ecg_adler_masked_ptr_kernel"},
+	{7, false, ecg_adler_masked_ptr_kernel<false>, "ecg_adler_masked_ptr_kernel<bytes>"},
+};
+
+const csum_entry<ecg_csum_masked_params_t> g_cells_ptr[] = {
+	{1, true, ecg_crc_cells_ptr_kernel<16, false, true, TK_4>, "ecg_crc_cells_ptr_kernel<crc16>"},
+	{1, false, ecg_crc_cells_ptr_kernel<16, false, false, TK_5>, "ecg_crc_cells_ptr_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_cells_ptr_kernel<32, true, true, TK_4>, "ecg_crc_cells_ptr_kernel<crc32>"},
+	{2, false, ecg_crc_cells_ptr_kernel<32, true, false, TK_5>, "ecg_crc_cells_ptr_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_cells_ptr_kernel<64, true, true, TK_4>, "ecg_crc_cells_ptr_kernel<crc64>"},
+	{3, false, ecg_crc_cells_ptr_kernel<64, true, false, TK_5>, "ecg_crc_cells_ptr_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_cells_ptr_kernel<true>, "ecg_adler_cells_ptr_kernel"},
+	{7, false, ecg_adler_cells_ptr_kernel<false>, "ecg_adler_cells_ptr_kernel<bytes>"},
+};
+
 template <class E, uint32_t N>
 constexpr uint32_t rows(const E (&)[N])
 {
@@ -810,6 +918,8 @@ constexpr uint32_t KID_GROUP = KID_SPLIT + rows(g_split);
 constexpr uint32_t KID_COMPARE = KID_GROUP + rows(g_group);
 constexpr uint32_t KID_MASK = KID_COMPARE + 1;
 constexpr uint32_t KID_MASKED = KID_MASK + 1;
+constexpr uint32_t KID_MASKED_PTR = KID_MASKED + rows(g_masked);
+constexpr uint32_t KID_CELLS_PTR = KID_MASKED_PTR + rows(g_masked_ptr);
 
 template <auto &T>
 const char *row_name(uint32_t i)
@@ -824,6 +934,8 @@ const struct {
 	{KID_SPLIT, rows(g_split), row_name<g_split>},
 	{KID_GROUP, rows(g_group), row_name<g_group>},
 	{KID_MASKED, rows(g_masked), row_name<g_masked>},
+	{KID_MASKED_PTR, rows(g_masked_ptr), row_name<g_masked_ptr>},
+	{KID_CELLS_PTR, rows(g_cells_ptr), row_name<g_cells_ptr>},
 };
 
 // Launch the (type, aligned) row of table t, whose ids start at `first`, on
@@ -850,18 +962,41 @@ extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void 
 					uint32_t *kernel_id)
 {
 	const uint64_t total = (uint64_t)p->nstripes * p->slots * p->nch;
-	// the chunks of every cell start 16-byte aligned only when all four are
-	const bool aligned = (((uint64_t)(uintptr_t)p->src | (uint64_t)p->stripe_stride | p->cell_bytes |
-			       p->chunk_bytes) & 15u) == 0;
+	const bool ptrs = p->cells_dev != nullptr;
+	// the chunks of every cell start 16-byte aligned only when all four are;
+	// of a cell table the host says so, and the sizes must agree
+	const bool aligned = ptrs ? !p->bytewise
+				  : (((uint64_t)(uintptr_t)p->src | (uint64_t)p->stripe_stride | p->cell_bytes |
+				      p->chunk_bytes) & 15u) == 0;
 
 	if (total == 0)
 		return (int)hipSuccess;
 	if (p->k == 0 || p->k > ECG_RM_MAX_K || p->p == 0 || p->p > ECG_RM_MAX_P || p->which == 0 || p->which > 3 ||
 	    p->slots > p->k + p->p || p->masks == nullptr || p->chunk_bytes == 0 ||
-	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes)
+	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes ||
+	    (ptrs && aligned && ((p->cell_bytes | p->chunk_bytes) & 15u)))
 		return (int)hipErrorInvalidValue;
 	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
+	if (ptrs)
+		return launch_row(g_masked_ptr, KID_MASKED_PTR, aligned, (total + CS_WAVES - 1) / CS_WAVES,
+				  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
 	return launch_row(g_masked, KID_MASKED, aligned, (total + CS_WAVES - 1) / CS_WAVES,
+			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
+}
+
+extern "C" int ecg_k_launch_csum_cells(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
+				       uint32_t *kernel_id)
+{
+	uint64_t total;
+
+	if (p->ncells == 0 || p->nch == 0)
+		return (int)hipSuccess;
+	if (p->cells_dev == nullptr || p->out == nullptr || p->chunk_bytes == 0 ||
+	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes ||
+	    __builtin_mul_overflow(p->ncells, (uint64_t)p->nch, &total) ||
+	    (!p->bytewise && ((p->cell_bytes | p->chunk_bytes) & 15u)))
+		return (int)hipErrorInvalidValue;
+	return launch_row(g_cells_ptr, KID_CELLS_PTR, !p->bytewise, (total + CS_WAVES - 1) / CS_WAVES,
 			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
 }
 

@@ -210,6 +210,12 @@ _SIGS = [
                                   C.c_int64, vp, C.c_uint, vp, vp, C.c_uint, vp]),
     ("ecg_recover_masks_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, vp,
                                          C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    ("ecg_csum_masked_ptrs", C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64,
+                                       C.c_uint32, C.POINTER(vp), vp, C.c_uint, vp, vp, C.c_uint, vp]),
+    ("ecg_csum_cells_ptrs", C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(vp),
+                                      vp, vp]),
+    ("ecg_recover_masks_ptrs_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
+                                              C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
     ("ecg_set_csum_all_route", C.c_int, [vp, C.c_uint32]),
 ]
 
@@ -671,9 +677,8 @@ class Context:
         """ecg_recover_masks_ptrs: recover_masks() over a table of cell addresses --
         cells[s*(k+p)+c]: device address of logical cell c of stripe s (or a ctypes array of
         c_void_p, passed as it is; the library has copied it when the call returns)."""
-        arr = cells if cells is None or isinstance(cells, C.Array) else (vp * len(cells))(*cells)
-        _chk(lib().ecg_recover_masks_ptrs(self.h, k, p, cell_bytes, nstripes, arr, masks, result, flags, stream),
-             "recover_masks_ptrs")
+        _chk(lib().ecg_recover_masks_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks, result,
+                                          flags, stream), "recover_masks_ptrs")
 
     def csum_extents(self, htype: int, chunksize: int, rec_size: int, rx_idx: int, rx_nr: int, buf: int,
                      ext_stride: int, n_ext: int, csums: int, stream=None):
@@ -744,6 +749,38 @@ class Context:
         _chk(lib().ecg_recover_masks_csum(self.h, k, p, cell_bytes, nstripes, stripes, stripe_stride, masks,
                                           result, flags, htype, chunksize, rec_size, csums, src_csums, stream),
              "recover_masks_csum")
+
+    @staticmethod
+    def _cell_table(cells):
+        """A host table of device addresses: a ctypes array of c_void_p as it is, else one built
+        from the sequence (the library has copied it when the call returns)."""
+        return cells if cells is None or isinstance(cells, C.Array) else (vp * len(cells))(*cells)
+
+    def csum_masked_ptrs(self, htype: int, chunksize: int, rec_size: int, k: int, p: int, cell_bytes: int,
+                         nstripes: int, cells: Sequence[int] | None, masks: int, which: int, csums: int,
+                         result: int, flags: int = 0, stream=None):
+        """ecg_csum_masked_ptrs: csum_masked() over a table of cell addresses,
+        cells[s*(k+p)+c] = logical cell c of stripe s, as recover_masks_ptrs() takes it."""
+        _chk(lib().ecg_csum_masked_ptrs(self.h, htype, chunksize, rec_size, k, p, cell_bytes, nstripes,
+                                        self._cell_table(cells), masks, which, csums, result, flags, stream),
+             "csum_masked_ptrs")
+
+    def csum_cells_ptrs(self, htype: int, chunksize: int, rec_size: int, cell_bytes: int,
+                        cells: Sequence[int] | None, csums: int, ncells: int | None = None, stream=None):
+        """ecg_csum_cells_ptrs: checksum every cell of a table, csums[i*nch + c] = chunk c of
+        cells[i]; over an [S][k+p] table the array csum_mask() reads.  ncells: len(cells)."""
+        _chk(lib().ecg_csum_cells_ptrs(self.h, htype, chunksize, rec_size, cell_bytes,
+                                       len(cells or ()) if ncells is None else ncells, self._cell_table(cells), csums,
+                                       stream), "csum_cells_ptrs")
+
+    def recover_masks_ptrs_csum(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None,
+                                masks: int, result: int, htype: int, chunksize: int, rec_size: int, csums: int,
+                                src_csums: int | None = None, flags: int = 0, stream=None):
+        """ecg_recover_masks_ptrs_csum: recover_masks_csum() over a table of cell addresses; the
+        table is staged once for the recovery and the checksum launches."""
+        _chk(lib().ecg_recover_masks_ptrs_csum(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks,
+                                               result, flags, htype, chunksize, rec_size, csums, src_csums,
+                                               stream), "recover_masks_ptrs_csum")
 
     def set_csum_all_route(self, route: int = 0):
         """Source checksums of *_csum_all: 0 measured default, 1 fused kernel, 2 two passes."""

@@ -195,6 +195,73 @@ int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, ui
 			   unsigned flags, int type, uint64_t chunksize, uint64_t rec_size,
 			   void *csums, void *src_csums, void *stream);
 
+/* ecg_csum_masked over a TABLE OF CELL ADDRESSES, the step after
+ * ecg_recover_masks_ptrs (ecg.h), whose table this is: cells, a HOST array of
+ * nstripes * (k + p) device addresses, cells[s*(k+p) + c] = logical cell c of
+ * stripe s, each cell_bytes long and at any byte.  The table is copied before
+ * the call returns (the caller may overwrite or free it at once).  The cells
+ * are read only: duplicate entries and overlapping cells are allowed.
+ * Everything else is ecg_csum_masked's, word for word: the cells
+ * ecg_csum_masked_sel picks for masks[s] and `which`, the [S][k+p][nch] slots of
+ * csums (at any byte; no byte outside the selected cells' slots is written),
+ * the four result words, {0, UINT64_MAX, 0, 0} when nstripes or cell_bytes is
+ * 0, ECG_RM_SPARSE accepted and ignored, ecg_set_csum_launch, `launches`
+ * advanced and `csum_chunks` not.  Every table index derives from the selection,
+ * which is empty for a word that is no valid set: all 2^32 mask values are safe,
+ * and a stripe with an invalid or zero mask reads no table entry.
+ * Errors, -ECG_DER_INVAL unless noted, in this order: ecg_csum_masked's own
+ * argument checks in its order and words (-ECG_DER_NOTSUPPORTED for an unknown
+ * hash type); a NULL context; cells == NULL with nstripes and cell_bytes
+ * non-zero; a NULL entry (named by its index; every entry is checked, selected
+ * or not); csums, masks or result sharing a byte with a cell ("overlaps", and
+ * the cell's index); csums overlapping masks.
+ * A table with cells[s*(k+p)+c] == cells[0] + s*stride + c*cell_bytes for one
+ * stride (negative too; one stripe always) whose arguments pass
+ * ecg_csum_masked's checks IS the call ecg_csum_masked(stripes = cells[0],
+ * stripe_stride = stride): no table is uploaded and ecg_last_kernel names the
+ * strided kernel.  Any other table runs ecg_crc_masked_ptr_kernel<type> /
+ * ecg_adler_masked_ptr_kernel with 16-byte loads when EVERY entry, cell_bytes
+ * and the record chunk size are multiples of 16, and their <..bytes> forms for
+ * the WHOLE launch when one is not. */
+int ecg_csum_masked_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
+			 int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			 void *const *cells, const uint32_t *masks, unsigned which,
+			 void *csums, void *result, unsigned flags, void *stream);
+
+/* Checksum EVERY cell of a table: cells, a host array of ncells device
+ * addresses as above; csums[i*nch + c] = the checksum of chunk c of cells[i],
+ * each cell taken as an extent from record index 0 (ecg_csum_len(type) bytes
+ * each; csums at any byte).  Over an [S][k+p] table, ncells = S*(k+p), that is
+ * the stripe-major array ecg_csum_mask reads (stripe_stride = (k+p)*nch,
+ * cell_stride = nch): the checksum-driven scrub over cell tables is
+ * ecg_csum_cells_ptrs -> ecg_memset(masks) -> ecg_csum_mask ->
+ * ecg_recover_masks_ptrs_csum, no host round trip.  No masks, no result; always
+ * the table kernels (ecg_crc_cells_ptr_kernel<type> / ecg_adler_cells_ptr_kernel,
+ * <..bytes> as above).  Telemetry: `csum_chunks` += ncells * nch, `launches`
+ * counts the launch.  Errors: -ECG_DER_NOTSUPPORTED for an unknown hash type;
+ * -ECG_DER_INVAL for chunksize or rec_size 0, cell_bytes % rec_size != 0, too
+ * many checksums, a NULL context, NULL cells or csums (ncells and cell_bytes
+ * non-zero), a NULL entry (named), csums overlapping a cell. */
+int ecg_csum_cells_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
+			uint64_t cell_bytes, uint64_t ncells, void *const *cells,
+			void *csums, void *stream);
+
+/* ecg_recover_masks_csum over a table of cell addresses: ecg_recover_masks_ptrs,
+ * then ECG_CM_ERASED into csums and, with src_csums, ECG_CM_SURVIVORS into
+ * src_csums (src_csums == csums: one which = 3 launch; any other overlap of
+ * the two is -ECG_DER_INVAL), on one stream.  result: ecg_recover_masks's four
+ * words.  The argument errors of both halves are returned before anything is
+ * queued, and the table is checked and staged ONCE for all its launches.  An
+ * affine table that passes ecg_recover_masks_ptrs's shortcut conditions (and
+ * whose checksum arrays are clear of the image) is the call
+ * ecg_recover_masks_csum(stripes = cells[0], stride).  As for
+ * ecg_recover_masks_ptrs, no cell the launch writes may overlap any other cell
+ * (not checked). */
+int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+				void *const *cells, const uint32_t *masks, void *result, unsigned flags,
+				int type, uint64_t chunksize, uint64_t rec_size,
+				void *csums, void *src_csums, void *stream);
+
 /* Route of the source checksums of ecg_encode_csum_all / ecg_recover_csum_all:
  * 0 the measured default per (hash type, k, output rows), 1 the fused kernel
  * wherever it can take the request, 2 always two passes.  Same results. */
