@@ -590,12 +590,29 @@ static int fused_kh(ecg_ctx_t *ctx, int type, uint64_t rcs, uint64_t last, uint3
 	return rc;
 }
 
+/* The CRC tables of a hash type (NULL for adler32, which has none).  Takes
+ * ctx->lock: fetched before a cell-table call opens its table. */
+static int hash_tbl(ecg_ctx_t *ctx, int type, const void **tbl)
+{
+	*tbl = NULL;
+	return type == ECG_HASH_ADLER32 ? 0 : crc_tables(ctx, type, tbl);
+}
+
+/* tbl / poly / init / xorout of a zeroed parameter block, which ecg_kabi.h's
+ * three have under these names (adler32 leaves them 0) */
+#define HASH_FILL(prm, type, table)                                                                           \
+	((type) == ECG_HASH_ADLER32                                                                           \
+		 ? (void)0                                                                                    \
+		 : (void)((prm)->tbl = (table), (prm)->poly = g_defs[type].poly,                              \
+			  (prm)->init = g_defs[type].init, (prm)->xorout = g_defs[type].xorout))
+
 int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
 		     uint64_t rx_idx, uint64_t rx_nr, const void *buf, int64_t ext_stride,
 		     uint32_t n_ext, void *csums, void *stream)
 {
 	ecg_csum_params_t prm;
 	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
+	const void *tbl;
 	uint64_t per, first_end;
 	uint32_t kid = 0;
 	int rc, e;
@@ -613,14 +630,10 @@ int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_
 	if (rc)
 		return rc;
 	memset(&prm, 0, sizeof(prm));
-	if (type != ECG_HASH_ADLER32) {
-		rc = crc_tables(ctx, type, &prm.tbl);
-		if (rc)
-			return rc;
-		prm.poly = g_defs[type].poly;
-		prm.init = g_defs[type].init;
-		prm.xorout = g_defs[type].xorout;
-	}
+	rc = hash_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	HASH_FILL(&prm, type, tbl);
 	/* chunk 0 runs from rx_idx to the end of its aligned chunk (clipped);
 	 * the rest are whole chunks, the last one clipped
 	 * (csum_recx_chunkidx2range, ref:src/common/checksum.c:1489-1565) */
@@ -849,14 +862,6 @@ static int masked_check(const char *fn, int type, uint64_t chunksize, uint64_t r
 	return 0;
 }
 
-/* The CRC tables of a hash type (NULL for adler32, which has none).  Takes
- * ctx->lock: fetched before a cell-table call locks its scratch slot. */
-static int masked_tbl(ecg_ctx_t *ctx, int type, const void **tbl)
-{
-	*tbl = NULL;
-	return type == ECG_HASH_ADLER32 ? 0 : crc_tables(ctx, type, tbl);
-}
-
 /* One ecg_csum_masked launch on st; result NULL = nothing counted.  Over the
  * strided image `stripes`, or with cells_dev over a staged cell table (bytewise:
  * an entry, C or the chunk size is no multiple of 16). */
@@ -869,12 +874,7 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const void *tbl, const struct
 	int e;
 
 	memset(&prm, 0, sizeof(prm));
-	if (type != ECG_HASH_ADLER32) {
-		prm.tbl = tbl;
-		prm.poly = g_defs[type].poly;
-		prm.init = g_defs[type].init;
-		prm.xorout = g_defs[type].xorout;
-	}
+	HASH_FILL(&prm, type, tbl);
 	prm.src = stripes;
 	prm.out = csums;
 	prm.masks = masks;
@@ -924,199 +924,202 @@ int ecg_csum_masked(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_s
 		return rc;
 	if (S == 0 || C == 0)
 		return 0;
-	rc = masked_tbl(ctx, type, &tbl);
+	rc = hash_tbl(ctx, type, &tbl);
 	if (rc)
 		return rc;
 	return masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks, which, csums,
 			     result, st);
 }
 
+/* What a composite (recovery, then the checksums of what it touched) makes of
+ * its arguments */
+struct composite {
+	struct masked_geom g;
+	int two;		/* src_csums is a second array: a SURVIVORS launch of its own */
+	unsigned first;		/* `which` of the launch into csums: both kinds when src_csums is csums */
+};
+
+/* Both halves' argument errors, but the NULL context, before anything is
+ * queued: ecg_recover_masks_check, then masked_check for csums and for a second
+ * src_csums.  table: a cell-table call (no stripes: the cells are checked entry
+ * by entry when the table is opened). */
+static int composite_check(const char *fn, int table, int k, int p, uint64_t C, uint32_t S, const void *stripes,
+			   int64_t stripe_stride, const uint32_t *masks, const void *result, unsigned flags, int type,
+			   uint64_t chunksize, uint64_t rec_size, const void *csums, const void *src_csums,
+			   struct composite *c)
+{
+	int rc;
+
+	c->two = src_csums != NULL && src_csums != csums;
+	c->first = src_csums != NULL && !c->two ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED;
+	rc = ecg_recover_masks_check(fn, 1, k, p, table ? 0 : C, S, stripes, stripe_stride, masks, result, flags);
+	if (rc == 0)
+		rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, table, stripes, stripe_stride, masks, c->first,
+				  csums, "csums", NULL, 0, flags, &c->g);
+	if (rc == 0 && c->two)
+		rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, table, stripes, stripe_stride, masks,
+				  ECG_CM_SURVIVORS, src_csums, "src_csums", NULL, 0, flags, &c->g);
+	if (rc == 0 && c->two && S && C && ranges_overlap(csums, c->g.bytes, src_csums, c->g.bytes))
+		rc = ecg_fail(-ECG_DER_INVAL, "%s: src_csums must be csums itself or not overlap it", fn);
+	return rc;
+}
+
 int ecg_recover_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *stripes,
 			   int64_t stripe_stride, const uint32_t *masks, void *result, unsigned flags, int type,
 			   uint64_t chunksize, uint64_t rec_size, void *csums, void *src_csums, void *stream)
 {
-	const int one = src_csums != NULL && src_csums == csums;	/* one array, one which = 3 launch */
-	struct masked_geom g;
+	struct composite c;
 	const void *tbl;
 	hipStream_t st;
 	int rc;
 
-	/* both halves' argument errors before anything is queued */
-	rc = ecg_recover_masks_check("recover_masks_csum", 1, k, p, C, S, stripes, stripe_stride, masks, result, flags);
+	rc = composite_check("recover_masks_csum", 0, k, p, C, S, stripes, stripe_stride, masks, result, flags, type,
+			     chunksize, rec_size, csums, src_csums, &c);
 	if (rc)
 		return rc;
-	rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, 0, stripes, stripe_stride, masks,
-			  one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, "csums", NULL, 0, flags, &g);
-	if (rc)
-		return rc;
-	if (src_csums != NULL && !one) {
-		rc = masked_check("recover_masks_csum", type, chunksize, rec_size, k, p, C, S, 0, stripes, stripe_stride,
-				  masks, ECG_CM_SURVIVORS, src_csums, "src_csums", NULL, 0, flags, &g);
-		if (rc)
-			return rc;
-		if (S && C && ranges_overlap(csums, g.bytes, src_csums, g.bytes))
-			return ecg_fail(-ECG_DER_INVAL,
-					"recover_masks_csum: src_csums must be csums itself or not overlap it");
-	}
 	if (ctx == NULL)
 		return ecg_fail(-ECG_DER_INVAL, "recover_masks_csum: NULL context");
 	rc = ecg_recover_masks(ctx, k, p, C, S, stripes, stripe_stride, masks, result, flags, stream);
 	if (rc || S == 0 || C == 0)
 		return rc;
-	st = ecg_pick_stream(ctx, stream);
-	rc = masked_tbl(ctx, type, &tbl);
+	rc = hash_tbl(ctx, type, &tbl);
 	if (rc)
 		return rc;
-	rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks,
-			   one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED, csums, NULL, st);
-	if (rc == 0 && src_csums != NULL && !one)
-		rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks,
+	st = ecg_pick_stream(ctx, stream);
+	rc = masked_launch(ctx, type, tbl, &c.g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks, c.first, csums, NULL,
+			   st);
+	if (rc == 0 && c.two)
+		rc = masked_launch(ctx, type, tbl, &c.g, k, p, C, S, stripes, stripe_stride, NULL, 0, masks,
 				   ECG_CM_SURVIVORS, src_csums, NULL, st);
 	return rc;
 }
 
 /*
- * The cell-table forms.  Each stages the caller's table as
- * ecg_recover_masks_ptrs stages its own (ecg_recover_masks.c): a scratch slot
- * reserved under ctx->lock, one pass of ecg_cell_table into its pinned half,
- * ecg_table_upload, the launches, and ecg_table_done.  Whatever takes ctx->lock
- * itself (the CRC tables, the set table) is fetched before.
+ * The cell-table forms.  Each stages the caller's table through the one path
+ * ecg_recover_masks_ptrs takes (ecg_recover_masks.c, ecg_internal.h): its
+ * argument checks, ecg_staged_open, its own overlap checks and affine test,
+ * ecg_staged_upload, the launches, ecg_staged_close.  Whatever takes ctx->lock
+ * itself (the CRC tables, the set table) is fetched before the open.
  */
+
+/* the byte-granular body for the whole launch: an entry, C or the chunk size
+ * (rcs; 0 for the recovery) is no multiple of 16 */
+static int table_bytewise(const struct ecg_staged *t, uint64_t C, uint64_t rcs)
+{
+	return (t->bits | C | rcs) % 16u != 0;
+}
 
 int ecg_csum_masked_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
 			 uint32_t S, void *const *cells, const uint32_t *masks, unsigned which, void *csums,
 			 void *result, unsigned flags, void *stream)
 {
-	struct ecg_scratch_slot *sc = NULL;
+	static const char fn[] = "csum_masked_ptrs";
+	const uint32_t n = (uint32_t)(k + p);
+	struct ecg_staged t;
 	struct masked_geom g;
 	const void *tbl;
-	uint64_t bits = 0;
-	int64_t stride = 0;
-	size_t tbytes;
 	hipStream_t st;
-	uint32_t n;
-	int rc, affine = 0;
+	int rc;
 
-	rc = masked_check("csum_masked_ptrs", type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, which, csums,
-			  "csums", result, 1, flags, &g);
+	rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, which, csums, "csums", result, 1,
+			  flags, &g);
 	if (rc)
 		return rc;
 	if (ctx == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: NULL context");
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
 	if (S && C && cells == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: NULL cells");
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells", fn);
 	rc = ecg_ctx_enter(ctx);
 	if (rc)
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
 	if (S == 0 || C == 0)	/* result = {0, UINT64_MAX, 0, 0} and nothing else */
 		return ecg_result_reset(result, st, "csum_masked_ptrs memset");
-	rc = masked_tbl(ctx, type, &tbl);
-	if (rc)
-		return rc;
-	n = (uint32_t)(k + p);
-	tbytes = (size_t)S * n * sizeof(uint64_t);
-
-	pthread_mutex_lock(&ctx->lock);
-	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	rc = hash_tbl(ctx, type, &tbl);
 	if (rc == 0) {
 		const struct ecg_clear clear[3] = {
 			{csums, g.bytes, "csums"}, {masks, 4ull * S, "masks"}, {result, 32, "result"}};
 
-		rc = ecg_cell_table("csum_masked_ptrs", sc->pin, cells, S, n, C, clear, 3, &bits, &affine, &stride);
+		rc = ecg_staged_open(ctx, fn, cells, S, n, C, clear, 3, &t);
 	}
-	if (rc == 0 && ranges_overlap(csums, g.bytes, masks, 4ull * S))
-		rc = ecg_fail(-ECG_DER_INVAL, "csum_masked_ptrs: csums overlaps the masks");
+	if (rc)
+		return rc;
+	if (ranges_overlap(csums, g.bytes, masks, 4ull * S))
+		return ecg_staged_close(ctx, &t, st, ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the masks", fn));
 	/* ecg_csum_masked's own layout, and csums clear of the whole image as it
 	 * demands: its launch, with no table */
-	if (rc == 0 && affine && !ecg_cells_overlap(csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C)) {
-		pthread_mutex_unlock(&ctx->lock);
-		return ecg_csum_masked(ctx, type, chunksize, rec_size, k, p, C, S, cells[0], stride, masks, which, csums,
+	if (t.affine && !ecg_cells_overlap(csums, g.bytes, cells[0], S, t.stride, n, (int64_t)C, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_csum_masked(ctx, type, chunksize, rec_size, k, p, C, S, cells[0], t.stride, masks, which, csums,
 				       result, flags, stream);
 	}
+	rc = ecg_staged_upload(&t, result, st, "csum_masked_ptrs memset", "csum_masked_ptrs cell table");
 	if (rc == 0)
-		rc = ecg_result_reset(result, st, "csum_masked_ptrs memset");
-	if (rc == 0)
-		rc = ecg_table_upload(sc, tbytes, st, "csum_masked_ptrs cell table");
-	if (rc == 0) {
-		rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0, masks,
+		rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, t.sc->dev, table_bytewise(&t, C, g.rcs), masks,
 				   which, csums, result, st);
-		rc = ecg_table_done(sc, st, rc);
-	}
-	pthread_mutex_unlock(&ctx->lock);
-	return rc;
+	return ecg_staged_close(ctx, &t, st, rc);
 }
 
 int ecg_csum_cells_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, uint64_t C, uint64_t ncells,
 			void *const *cells, void *csums, void *stream)
 {
+	static const char fn[] = "csum_cells_ptrs";
 	const int cl = ecg_csum_len(type);
 	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
-	struct ecg_scratch_slot *sc = NULL;
 	ecg_csum_masked_params_t prm;
-	uint64_t nch, bytes, bits = 0;
-	int64_t stride = 0;
+	struct ecg_staged t;
+	const void *tbl;
+	uint64_t nch, bytes;
 	uint32_t kid = 0;
 	hipStream_t st;
-	size_t tbytes;
-	int rc, e, affine = 0;
+	int rc, e;
 
 	if (cl < 0)
-		return ecg_fail(-ECG_DER_NOTSUPPORTED, "csum_cells_ptrs: hash type %d not supported", type);
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "%s: hash type %d not supported", fn, type);
 	if (rcs == 0)
-		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: chunksize and rec_size must not be 0");
+		return ecg_fail(-ECG_DER_INVAL, "%s: chunksize and rec_size must not be 0", fn);
 	if (C % rec_size)
-		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: cell_bytes %llu is not a multiple of rec_size %llu",
+		return ecg_fail(-ECG_DER_INVAL, "%s: cell_bytes %llu is not a multiple of rec_size %llu", fn,
 				(unsigned long long)C, (unsigned long long)rec_size);
 	nch = C / rcs + (C % rcs != 0);
 	if (nch > UINT32_MAX || __builtin_mul_overflow(nch * (uint64_t)cl, ncells, &bytes) ||
 	    ncells > SIZE_MAX / sizeof(uint64_t))
-		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: too many checksums");
+		return ecg_fail(-ECG_DER_INVAL, "%s: too many checksums", fn);
 	if (ctx == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: NULL context");
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
 	if (ncells && C && (cells == NULL || csums == NULL))
-		return ecg_fail(-ECG_DER_INVAL, "csum_cells_ptrs: NULL cells or csums");
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells or csums", fn);
 	rc = ecg_ctx_enter(ctx);
 	if (rc || ncells == 0 || C == 0)
 		return rc;
 	st = ecg_pick_stream(ctx, stream);
-	memset(&prm, 0, sizeof(prm));
-	rc = masked_tbl(ctx, type, &prm.tbl);
-	if (rc)
-		return rc;
-	if (type != ECG_HASH_ADLER32) {
-		prm.poly = g_defs[type].poly;
-		prm.init = g_defs[type].init;
-		prm.xorout = g_defs[type].xorout;
-	}
-	tbytes = (size_t)ncells * sizeof(uint64_t);
-
-	pthread_mutex_lock(&ctx->lock);
-	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
+	rc = hash_tbl(ctx, type, &tbl);
 	if (rc == 0) {
 		const struct ecg_clear clear = {csums, bytes, "csums"};
 
 		/* a table of ncells rows of one cell; no affine route: ecg_csum_extents
 		 * wants csums aligned and picks its kernels by shape */
-		rc = ecg_cell_table("csum_cells_ptrs", sc->pin, cells, ncells, 1, C, &clear, 1, &bits, &affine, &stride);
+		rc = ecg_staged_open(ctx, fn, cells, ncells, 1, C, &clear, 1, &t);
 	}
-	if (rc == 0)
-		rc = ecg_table_upload(sc, tbytes, st, "csum_cells_ptrs cell table");
-	if (rc == 0) {
-		prm.out = csums;
-		prm.cells_dev = sc->dev;
-		prm.bytewise = (bits | C | rcs) % 16u != 0;
-		prm.cell_bytes = C;
-		prm.chunk_bytes = rcs;
-		prm.ncells = ncells;
-		prm.nch = (uint32_t)nch;
-		prm.type = (uint32_t)type;
-		ecg_trace_push("ecg:csum_cells_ptrs");
-		e = ecg_k_launch_csum_cells(&prm, (void *)st, ctx->csum_blocks, &kid);
-		rc = ecg_launch_done(ctx, e, "csum_cells_ptrs kernel launch", 1, ecg_k_kernel_name(kid));
-		rc = ecg_table_done(sc, st, rc);
-	}
-	pthread_mutex_unlock(&ctx->lock);
+	if (rc)
+		return rc;
+	rc = ecg_staged_upload(&t, NULL, st, NULL, "csum_cells_ptrs cell table");
+	if (rc)
+		return ecg_staged_close(ctx, &t, st, rc);
+	memset(&prm, 0, sizeof(prm));
+	HASH_FILL(&prm, type, tbl);
+	prm.out = csums;
+	prm.cells_dev = t.sc->dev;
+	prm.bytewise = (uint32_t)table_bytewise(&t, C, rcs);
+	prm.cell_bytes = C;
+	prm.chunk_bytes = rcs;
+	prm.ncells = ncells;
+	prm.nch = (uint32_t)nch;
+	prm.type = (uint32_t)type;
+	ecg_trace_push("ecg:csum_cells_ptrs");
+	e = ecg_k_launch_csum_cells(&prm, (void *)st, ctx->csum_blocks, &kid);
+	rc = ecg_launch_done(ctx, e, "csum_cells_ptrs kernel launch", 1, ecg_k_kernel_name(kid));
+	rc = ecg_staged_close(ctx, &t, st, rc);
 	if (rc == 0)
 		ECG_STAT_ADD(ctx, csum_chunks, ncells * nch);
 	return rc;
@@ -1127,36 +1130,17 @@ int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32
 				uint64_t rec_size, void *csums, void *src_csums, void *stream)
 {
 	static const char fn[] = "recover_masks_ptrs_csum";
-	const int one = src_csums != NULL && src_csums == csums;	/* one array, one which = 3 launch */
-	const int two = src_csums != NULL && !one;
-	const unsigned first = one ? ECG_CM_ERASED | ECG_CM_SURVIVORS : ECG_CM_ERASED;
-	struct ecg_scratch_slot *sc = NULL;
+	const uint32_t n = (uint32_t)(k + p);
 	const void *settbl = NULL, *tbl;
-	struct masked_geom g;
-	uint64_t bits = 0;
-	int64_t stride = 0;
-	size_t tbytes;
+	struct ecg_staged t;
+	struct composite c;
 	hipStream_t st;
-	uint32_t n;
-	int rc, affine = 0;
+	int rc;
 
-	/* both halves' argument errors before anything is queued (no stripes: the
-	 * cells are checked entry by entry below) */
-	rc = ecg_recover_masks_check(fn, 1, k, p, 0, S, NULL, 0, masks, result, flags);
+	rc = composite_check(fn, 1, k, p, C, S, NULL, 0, masks, result, flags, type, chunksize, rec_size, csums, src_csums,
+			     &c);
 	if (rc)
 		return rc;
-	rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, first, csums, "csums", NULL, 0,
-			  flags, &g);
-	if (rc)
-		return rc;
-	if (two) {
-		rc = masked_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, masks, ECG_CM_SURVIVORS,
-				  src_csums, "src_csums", NULL, 0, flags, &g);
-		if (rc)
-			return rc;
-		if (S && C && ranges_overlap(csums, g.bytes, src_csums, g.bytes))
-			return ecg_fail(-ECG_DER_INVAL, "%s: src_csums must be csums itself or not overlap it", fn);
-	}
 	if (ctx == NULL)
 		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
 	if (S && C && cells == NULL)
@@ -1169,53 +1153,42 @@ int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32
 		return ecg_result_reset(result, st, "recover_masks_ptrs_csum memset");
 	rc = ecg_rm_settbl(ctx, k, p, &settbl);
 	if (rc == 0)
-		rc = masked_tbl(ctx, type, &tbl);
+		rc = hash_tbl(ctx, type, &tbl);
+	if (rc == 0) {
+		/* the table is checked and staged once for the two or three launches */
+		const struct ecg_clear clear[4] = {{masks, 4ull * S, "masks"}, {result, 32, "result"},
+						   {csums, c.g.bytes, "csums"},
+						   {src_csums, c.two ? c.g.bytes : 0, "src_csums"}};
+
+		rc = ecg_staged_open(ctx, fn, cells, S, n, C, clear, 4, &t);
+	}
 	if (rc)
 		return rc;
-	n = (uint32_t)(k + p);
-	tbytes = (size_t)S * n * sizeof(uint64_t);
-
-	/* the table is checked and staged once for the two or three launches */
-	pthread_mutex_lock(&ctx->lock);
-	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
-	if (rc == 0) {
-		const struct ecg_clear clear[4] = {{masks, 4ull * S, "masks"}, {result, 32, "result"},
-						   {csums, g.bytes, "csums"},
-						   {src_csums, two ? g.bytes : 0, "src_csums"}};
-
-		rc = ecg_cell_table(fn, sc->pin, cells, S, n, C, clear, 4, &bits, &affine, &stride);
-	}
-	if (rc == 0 && ranges_overlap(csums, g.bytes, masks, 4ull * S))
-		rc = ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the masks", fn);
-	if (rc == 0 && two && ranges_overlap(src_csums, g.bytes, masks, 4ull * S))
-		rc = ecg_fail(-ECG_DER_INVAL, "%s: src_csums overlaps the masks", fn);
+	if (ranges_overlap(csums, c.g.bytes, masks, 4ull * S))
+		return ecg_staged_close(ctx, &t, st, ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the masks", fn));
+	if (c.two && ranges_overlap(src_csums, c.g.bytes, masks, 4ull * S))
+		return ecg_staged_close(ctx, &t, st, ecg_fail(-ECG_DER_INVAL, "%s: src_csums overlaps the masks", fn));
 	/* the layout of ecg_recover_masks_csum, and masks and the checksum arrays
 	 * clear of the whole image as it demands: that call, with no table */
-	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C) &&
-	    !ecg_cells_overlap(csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C) &&
-	    !(two && ecg_cells_overlap(src_csums, g.bytes, cells[0], S, stride, n, (int64_t)C, C))) {
-		pthread_mutex_unlock(&ctx->lock);
-		return ecg_recover_masks_csum(ctx, k, p, C, S, cells[0], stride, masks, result, flags, type, chunksize,
+	if (t.affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, t.stride, n, (int64_t)C, C) &&
+	    !ecg_cells_overlap(csums, c.g.bytes, cells[0], S, t.stride, n, (int64_t)C, C) &&
+	    !(c.two && ecg_cells_overlap(src_csums, c.g.bytes, cells[0], S, t.stride, n, (int64_t)C, C))) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_recover_masks_csum(ctx, k, p, C, S, cells[0], t.stride, masks, result, flags, type, chunksize,
 					      rec_size, csums, src_csums, stream);
 	}
+	rc = ecg_staged_upload(&t, result, st, "recover_masks_ptrs_csum memset", "recover_masks_ptrs_csum cell table");
 	if (rc == 0)
-		rc = ecg_result_reset(result, st, "recover_masks_ptrs_csum memset");
-	if (rc == 0)
-		rc = ecg_table_upload(sc, tbytes, st, "recover_masks_ptrs_csum cell table");
-	if (rc == 0) {
-		rc = ecg_rm_launch(ctx, fn, settbl, k, p, C, S, NULL, 0, sc->dev, (bits | C) % 16u != 0, masks, result,
+		rc = ecg_rm_launch(ctx, fn, settbl, k, p, C, S, NULL, 0, t.sc->dev, table_bytewise(&t, C, 0), masks, result,
 				   flags, st);
-		if (rc == 0)
-			rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0,
-					   masks, first, csums, NULL, st);
-		if (rc == 0 && two)
-			rc = masked_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, sc->dev, (bits | C | g.rcs) % 16u != 0,
-					   masks, ECG_CM_SURVIVORS, src_csums, NULL, st);
-		/* the fetch and every kernel above read the slot: the next user waits */
-		rc = ecg_table_done(sc, st, rc);
-	}
-	pthread_mutex_unlock(&ctx->lock);
-	return rc;
+	if (rc == 0)
+		rc = masked_launch(ctx, type, tbl, &c.g, k, p, C, S, NULL, 0, t.sc->dev, table_bytewise(&t, C, c.g.rcs),
+				   masks, c.first, csums, NULL, st);
+	if (rc == 0 && c.two)
+		rc = masked_launch(ctx, type, tbl, &c.g, k, p, C, S, NULL, 0, t.sc->dev, table_bytewise(&t, C, c.g.rcs),
+				   masks, ECG_CM_SURVIVORS, src_csums, NULL, st);
+	/* the fetch and every kernel above read the slot */
+	return ecg_staged_close(ctx, &t, st, rc);
 }
 
 /* Fused product + checksum parameters (ecg_kabi.h) for output cells of C

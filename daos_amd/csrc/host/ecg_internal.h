@@ -133,9 +133,12 @@ int ecg_scratch_reserve(ecg_ctx_t *ctx, size_t pin_bytes, size_t dev_bytes,
 /* The first `bytes` of sc->pin to sc->dev, queued on st (a fetch kernel:
  * ecg_k_launch_fetch); `what` names the table in the error. */
 int ecg_table_upload(struct ecg_scratch_slot *sc, size_t bytes, hipStream_t st, const char *what);
-/* After the last launch queued on st that reads the slot (rc: how the launches
- * went): its `done` event, for which the slot's next user waits (ctx->lock
- * held).  Returns rc, or the event's failure when rc was 0. */
+/* The release rule of a slot: once ecg_table_upload has returned 0 for it,
+ * every way out of the caller comes here, after the last launch queued on st
+ * that reads the slot and however those launches went (rc) -- the fetch reads
+ * the pinned half even when nothing follows it.  Records `done` and marks the
+ * slot pending, so its next user waits (ctx->lock held); nowhere else does
+ * either.  Returns rc, or the event's failure when rc was 0. */
 int ecg_table_done(struct ecg_scratch_slot *sc, hipStream_t st, int rc);
 
 /* batched segment copies (ecg_sgl.c).  A fixed list (cap preset, fixed = 1)
@@ -182,12 +185,27 @@ struct ecg_clear {
 	uint64_t len;
 	const char *what;
 };
-/* One pass over the caller's table of S x n addresses of cells of C bytes into
- * tab (the pinned half of a scratch slot): -ECG_DER_INVAL for a NULL entry or
- * a `clear` range inside a cell, naming `fn` and the entry; *bits = the OR of
- * the addresses, *affine = the table is cells[0] + s * *stride + c * C. */
-int ecg_cell_table(const char *fn, uint64_t *tab, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
-		   const struct ecg_clear *clear, int nclear, uint64_t *bits, int *affine, int64_t *stride);
+/* A caller's table of S x n addresses of cells of C bytes in a scratch slot,
+ * ctx->lock held.  A call is: its argument checks, open, its own overlap
+ * checks and affine test, upload, its launches, and close on every way out. */
+struct ecg_staged {
+	struct ecg_scratch_slot *sc;
+	size_t bytes;		/* of the table */
+	uint64_t bits;		/* OR of the addresses: the lane choice */
+	int64_t stride;		/* of the strided image it is, if affine */
+	int affine;		/* every entry is cells[0] + s * stride + c * C */
+	int queued;		/* the upload is: close releases the slot */
+};
+/* Locks, reserves a slot and passes once over the table: -ECG_DER_INVAL for a
+ * NULL entry or a `clear` range inside a cell, naming `fn` and the entry.  On
+ * failure closed: unlocked and nothing held. */
+int ecg_staged_open(ecg_ctx_t *ctx, const char *fn, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
+		    const struct ecg_clear *clear, int nclear, struct ecg_staged *t);
+/* ecg_result_reset (result NULL: none), then ecg_table_upload; their error texts */
+int ecg_staged_upload(struct ecg_staged *t, void *result, hipStream_t st, const char *reset, const char *what);
+/* ecg_table_done if the upload was queued (else nothing was: the affine route,
+ * a later argument error), then unlocks; returns what ecg_table_done would */
+int ecg_staged_close(ecg_ctx_t *ctx, struct ecg_staged *t, hipStream_t st, int rc);
 /* the set table of (k, p), built on first use; takes ctx->lock */
 int ecg_rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl);
 /* the recover_masks launch over the strided image `stripes`, or with cells_dev

@@ -11,9 +11,10 @@
  * ecg_mm_ptr_kernel.
  *
  * Scratch (per context, ctx->lock): pinned staging + device copy of the
- * pointer table, and device space for cells gathered from several iovs.  The
- * event `done` is recorded after every launch that reads the scratch; the
- * next user waits for it before overwriting, whatever its stream.
+ * pointer table, and device space for cells gathered from several iovs, two
+ * slots used in turn.  Every user of a slot (here, segs_submit of ecg_sgl.c,
+ * the staged cell tables of ecg_recover_masks.c) releases it by the rule of
+ * ecg_table_done (ecg_internal.h); the next user waits, whatever its stream.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -208,6 +209,30 @@ static int launch_ptrs(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, vo
 	return ecg_k_launch_matmul_ptrs(p, a->cells_dev, a->granule, cfg, stream, kid);
 }
 
+/* The product over the table a->cells_dev, through the launch tuner like the
+ * strided product: wide stripes probe the blocks-per-CU cap per (shape,
+ * pointer-table layout). */
+static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k, int rows, const unsigned char *coef,
+			  uint64_t C, uint32_t S, hipStream_t st, uint32_t *kid)
+{
+	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
+	int ke;
+
+	if (prm == NULL)
+		return ecg_fail(-ECG_DER_NOMEM, "matmul_ptrs: calloc");
+	ecg_gf_init();
+	prm->cell_bytes = C;
+	prm->nstripes = S;
+	prm->k = (uint32_t)k;
+	prm->rows = (uint32_t)rows;
+	for (int r = 0; r < rows; r++)
+		for (int j = 0; j < k; j++)
+			ecg_build_ptbl(coef[(size_t)r * k + j], &prm->tbl[r][j]);
+	ke = ecg_tune_launch_fn(ctx, prm, (uint32_t)a->granule, ECG_TUNE_LAYOUT_PTRS, launch_ptrs, a, st, kid);
+	free(prm);
+	return ke ? ecg_hip_fail((hipError_t)ke, "pointer-table kernel launch") : 0;
+}
+
 /* Table already in sc->pin (S x (k+rows) entries); copy, launch, record
  * (ctx->lock held).  With `gather`, its segment table follows the pointer
  * table at byte seg_off of the slot (pinned and device alike): both travel in
@@ -216,55 +241,31 @@ static int launch_table(ecg_ctx_t *ctx, struct ecg_scratch_slot *sc, int k, int 
 			const unsigned char *coef, uint64_t C, uint32_t S, hipStream_t st,
 			const struct ecg_segs *gather, size_t seg_off)
 {
-	const int granule = ptr_granule((const uint64_t *)sc->pin, S, k, rows, (int)ctx->cfg.no_unaligned);
+	const struct ptr_launch_arg a = {sc->dev,
+					 ptr_granule((const uint64_t *)sc->pin, S, k, rows, (int)ctx->cfg.no_unaligned)};
 	size_t tbytes = (size_t)S * (size_t)(k + rows) * sizeof(uint64_t);
-	ecg_mm_params_t *prm;
 	uint32_t kid = 0;
-	hipError_t e;
-	int r, j, ke, done;
+	int rc, done;
 
 	if (!(gather && gather->n)) {	/* no gather copies: maybe the offset kernel's layout */
-		r = launch_affine(ctx, (const uint64_t *)sc->pin, k, rows, coef, C, S, st, &done);
+		rc = launch_affine(ctx, (const uint64_t *)sc->pin, k, rows, coef, C, S, st, &done);
 		if (done)
-			return r;
+			return rc;
 	}
 	if (gather && gather->n)
 		tbytes = seg_off + gather->n * sizeof(ecg_copy_seg_t);
-	r = ecg_table_upload(sc, tbytes, st, "pointer table");
-	if (r)
-		return r;
-	if (gather && gather->n) {
-		r = ecg_segs_launch(gather, (unsigned char *)sc->dev + seg_off, st);
-		if (r)
-			return r;
-	}
-	prm = calloc(1, sizeof(*prm));
-	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "matmul_ptrs: calloc");
-	ecg_gf_init();
-	prm->cell_bytes = C;
-	prm->nstripes = S;
-	prm->k = (uint32_t)k;
-	prm->rows = (uint32_t)rows;
-	for (r = 0; r < rows; r++)
-		for (j = 0; j < k; j++)
-			ecg_build_ptbl(coef[(size_t)r * k + j], &prm->tbl[r][j]);
-	{
-		/* through the launch tuner like the strided product: wide stripes
-		 * probe the blocks-per-CU cap per (shape, pointer-table layout) */
-		const struct ptr_launch_arg a = {(const uint64_t *)sc->dev, granule};
-
-		ke = ecg_tune_launch_fn(ctx, prm, (uint32_t)granule, ECG_TUNE_LAYOUT_PTRS, launch_ptrs, &a, st, &kid);
-	}
-	free(prm);
-	if (ke != 0)
-		return ecg_hip_fail((hipError_t)ke, "pointer-table kernel launch");
-	e = hipEventRecord(sc->done, st);
-	if (e != hipSuccess)
-		return ecg_hip_fail(e, "scratch event record");
-	sc->pending = 1;
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
-	return 0;
+	rc = ecg_table_upload(sc, tbytes, st, "pointer table");
+	if (rc)
+		return rc;
+	/* the fetch is queued: whatever fails below, out through ecg_table_done */
+	if (gather && gather->n)
+		rc = ecg_segs_launch(gather, (unsigned char *)sc->dev + seg_off, st);
+	if (rc == 0)
+		rc = launch_product(ctx, &a, k, rows, coef, C, S, st, &kid);
+	rc = ecg_table_done(sc, st, rc);
+	if (rc == 0)
+		ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	return rc;
 }
 
 int ecg_matmul_ptrs(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, uint64_t cell_bytes,
@@ -634,7 +635,7 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 	if (rc == 0) {
 		uint64_t *t = sc->pin;
 		uint32_t at = 0, w, i;
-		hipError_t e;
+		int queued;
 
 		/* records launch by launch: launch w is the records [start_w, at) */
 		for (w = 0; w < nwave; w++) {
@@ -659,6 +660,7 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 			}
 		}
 		rc = ecg_table_upload(sc, (size_t)nit * rec * sizeof(uint64_t), st, "update table");
+		queued = rc == 0;
 		UPT(5);
 		for (w = 0, at = 0; w < nwave && rc == 0; w++) {
 			uint32_t cnt = 0;
@@ -674,12 +676,8 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 			at += cnt;
 		}
 		UPT(6);
-		if (rc == 0) {
-			e = hipEventRecord(sc->done, st);
-			if (e != hipSuccess)
-				rc = ecg_hip_fail(e, "scratch event record");
-			sc->pending = rc == 0;
-		}
+		if (queued)	/* however the launches went */
+			rc = ecg_table_done(sc, st, rc);
 		UPT(7);
 #ifdef ECG_QUEUE_TIMING
 		for (int i = 0; i < 7; i++)

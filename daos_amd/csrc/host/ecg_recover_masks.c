@@ -19,15 +19,16 @@
  * for k = 16, p = 3, the largest.
  *
  * ecg_recover_masks_ptrs is the same launch for stripes that are not one
- * strided image: a host table of cell addresses, staged through a scratch slot
- * as ecg_matmul_ptrs stages its own (ecg_ptrs.c), and the cell-table kernels
- * of the same file.  A table that is a strided image after all is handed to
+ * strided image: a host table of cell addresses and the cell-table kernels of
+ * the same file.  A table that is a strided image after all is handed to
  * ecg_recover_masks.
  *
- * The pass over such a table (ecg_cell_table), the set table's fetch and the
- * launch are shared with the cell-table checksum calls of ecg_csum.c, which
- * stage the same table (ecg_csum_masked_ptrs, ecg_csum_cells_ptrs) and run this
- * launch in front of theirs (ecg_recover_masks_ptrs_csum).
+ * How such a table gets to the device is here once, for this call and for the
+ * cell-table checksum calls of ecg_csum.c (ecg_csum_masked_ptrs,
+ * ecg_csum_cells_ptrs, ecg_recover_masks_ptrs_csum): ecg_staged_open (a scratch
+ * slot under ctx->lock and the one checking pass over the table), _drop,
+ * _upload and _close (ecg_internal.h).  The set table's fetch and the launch
+ * are shared with the composite, which runs this launch in front of its own.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -214,63 +215,87 @@ int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 			     ((uintptr_t)stripes | (uint64_t)stripe_stride | C) % 16u != 0, masks, result, flags, st);
 }
 
-/* One pass over a caller's table of S x n cell addresses for the call `fn`,
- * copying it into `tab` (the pinned half of a scratch slot): a NULL entry fails,
- * and so does any of the nclear ranges `clear` sharing a byte with a cell of C
- * bytes (an empty range shares none); *bits = the OR of the addresses (the lane
- * choice); *affine = every entry is cells[0] + s * *stride + c * C, the layout
- * of a strided image (S == 1: any stride). */
-int ecg_cell_table(const char *fn, uint64_t *tab, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
-		   const struct ecg_clear *clear, int nclear, uint64_t *bits, int *affine, int64_t *stride)
+/* The one staging path of the cell-table calls (ecg_internal.h); the table is
+ * staged as ecg_matmul_ptrs stages its own, so the caller's array is free again
+ * when the call returns.  The pass: a NULL entry fails, and so does any of the
+ * nclear ranges `clear` sharing a byte with a cell of C bytes (an empty range
+ * shares none); S == 1 is affine at any stride. */
+int ecg_staged_open(ecg_ctx_t *ctx, const char *fn, void *const *cells, uint64_t S, uint32_t n, uint64_t C,
+		    const struct ecg_clear *clear, int nclear, struct ecg_staged *t)
 {
 	const uint64_t c0 = (uint64_t)(uintptr_t)cells[0];
 	const uint64_t st = S > 1 ? (uint64_t)(uintptr_t)cells[n] - c0 : (uint64_t)n * C;
-	uint64_t all = 0;
-	int aff = 1;
+	uint64_t *tab, all = 0;
+	int rc, aff = 1;
 
+	*t = (struct ecg_staged){.bytes = (size_t)S * n * sizeof(uint64_t), .stride = (int64_t)st};
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, t->bytes, t->bytes, &t->sc);
+	if (rc)
+		return ecg_staged_close(ctx, t, NULL, rc);
+	tab = t->sc->pin;
 	for (uint64_t s = 0; s < S; s++)
 		for (uint32_t c = 0; c < n; c++) {
 			const size_t i = (size_t)(s * n + c);
 			const uint64_t a = (uint64_t)(uintptr_t)cells[i];
 
 			if (a == 0)
-				return ecg_fail(-ECG_DER_INVAL, "%s: NULL cell %zu", fn, i);
+				return ecg_staged_close(ctx, t, NULL, ecg_fail(-ECG_DER_INVAL, "%s: NULL cell %zu", fn, i));
 			for (int r = 0; r < nclear; r++) {
 				const uint64_t r0 = (uint64_t)(uintptr_t)clear[r].at;
 
 				if (clear[r].len && r0 < a + C && a < r0 + clear[r].len)
-					return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps cell %zu", fn, clear[r].what,
-							i);
+					return ecg_staged_close(ctx, t, NULL,
+								ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps cell %zu", fn,
+									 clear[r].what, i));
 			}
 			tab[i] = a;
 			all |= a;
 			aff &= a == c0 + s * st + c * C;
 		}
-	*bits = all;
-	*affine = aff;
-	*stride = (int64_t)st;
+	t->bits = all;
+	t->affine = aff;
 	return 0;
+}
+
+int ecg_staged_upload(struct ecg_staged *t, void *result, hipStream_t st, const char *reset, const char *what)
+{
+	int rc = result ? ecg_result_reset(result, st, reset) : 0;
+
+	if (rc == 0)
+		rc = ecg_table_upload(t->sc, t->bytes, st, what);
+	t->queued = rc == 0;
+	return rc;
+}
+
+int ecg_staged_close(ecg_ctx_t *ctx, struct ecg_staged *t, hipStream_t st, int rc)
+{
+	if (t->queued)
+		rc = ecg_table_done(t->sc, st, rc);
+	pthread_mutex_unlock(&ctx->lock);
+	return rc;
 }
 
 int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
 			   const uint32_t *masks, void *result, unsigned flags, void *stream)
 {
+	static const char fn[] = "recover_masks_ptrs";
+	/* the kernel reads mask words and counts into result while other blocks
+	 * write cells */
+	const struct ecg_clear clear[2] = {{masks, 4ull * S, "masks"}, {result, 32, "result"}};
 	const uint32_t n = (uint32_t)(k + p);
-	const size_t tbytes = (size_t)S * n * sizeof(uint64_t);
-	struct ecg_scratch_slot *sc = NULL;
 	const void *settbl = NULL;
-	uint64_t bits = 0;
-	int64_t stride = 0;
+	struct ecg_staged t;
 	hipStream_t st;
-	int rc, affine = 0;
+	int rc;
 
 	/* the checks that need no device, in ecg_recover_masks's order and
 	 * words (no stripes: the cells are checked entry by entry below) */
-	rc = ecg_recover_masks_check("recover_masks_ptrs", ctx != NULL, k, p, 0, S, NULL, 0, masks, result, flags);
+	rc = ecg_recover_masks_check(fn, ctx != NULL, k, p, 0, S, NULL, 0, masks, result, flags);
 	if (rc)
 		return rc;
 	if (S && C && cells == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "recover_masks_ptrs: NULL cells");
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells", fn);
 	rc = ecg_ctx_enter(ctx);
 	if (rc)
 		return rc;
@@ -278,37 +303,20 @@ int ecg_recover_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (S == 0 || C == 0)	/* nothing recovered, nothing left */
 		return ecg_result_reset(result, st, "recover_masks_ptrs memset");
 
-	rc = ecg_rm_settbl(ctx, k, p, &settbl);	/* ecg_recover_masks's */
+	rc = ecg_rm_settbl(ctx, k, p, &settbl);	/* ecg_recover_masks's; takes the lock: before open */
+	if (rc == 0)
+		rc = ecg_staged_open(ctx, fn, cells, S, n, C, clear, 2, &t);
 	if (rc)
 		return rc;
-
-	/* the table is staged as ecg_matmul_ptrs stages its own: the caller's
-	 * array is free again when this returns */
-	pthread_mutex_lock(&ctx->lock);
-	rc = ecg_scratch_reserve(ctx, tbytes, tbytes, &sc);
-	if (rc == 0) {
-		/* the kernel reads mask words and counts into result while other
-		 * blocks write cells */
-		const struct ecg_clear clear[2] = {{masks, 4ull * S, "masks"}, {result, 32, "result"}};
-
-		rc = ecg_cell_table("recover_masks_ptrs", sc->pin, cells, S, n, C, clear, 2, &bits, &affine, &stride);
-	}
 	/* ecg_recover_masks's own layout (and masks clear of the whole image, as
 	 * it demands): its launch, with no table and no dependent address loads */
-	if (rc == 0 && affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, stride, n, (int64_t)C, C)) {
-		pthread_mutex_unlock(&ctx->lock);
-		return ecg_recover_masks(ctx, k, p, C, S, cells[0], stride, masks, result, flags, stream);
+	if (t.affine && !ecg_cells_overlap(masks, 4ull * S, cells[0], S, t.stride, n, (int64_t)C, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_recover_masks(ctx, k, p, C, S, cells[0], t.stride, masks, result, flags, stream);
 	}
+	rc = ecg_staged_upload(&t, result, st, "recover_masks_ptrs memset", "recover_masks_ptrs cell table");
 	if (rc == 0)
-		rc = ecg_result_reset(result, st, "recover_masks_ptrs memset");
-	if (rc == 0)
-		rc = ecg_table_upload(sc, tbytes, st, "recover_masks_ptrs cell table");
-	if (rc == 0) {
-		rc = ecg_rm_launch(ctx, "recover_masks_ptrs", settbl, k, p, C, S, NULL, 0, sc->dev,
-				   (bits | C) % 16u != 0, masks, result, flags, st);
-		/* the fetch (and the kernel) read the slot: the next user waits */
-		rc = ecg_table_done(sc, st, rc);
-	}
-	pthread_mutex_unlock(&ctx->lock);
-	return rc;
+		rc = ecg_rm_launch(ctx, fn, settbl, k, p, C, S, NULL, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks, result,
+				   flags, st);
+	return ecg_staged_close(ctx, &t, st, rc);
 }

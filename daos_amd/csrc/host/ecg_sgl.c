@@ -83,11 +83,10 @@ static int segs_submit(ecg_ctx_t *ctx, const struct ecg_segs *v, hipStream_t st)
 		return rc;
 	memcpy(sc->pin, v->seg, b);
 	rc = ecg_table_upload(sc, b, st, "segment table");
-	if (rc == 0)
-		rc = ecg_segs_launch(v, sc->dev, st);
-	if (hipEventRecord(sc->done, st) == hipSuccess)	/* the H2D may still read pin */
-		sc->pending = 1;
-	return rc;
+	if (rc)
+		return rc;
+	/* the fetch may still read pin, however the launch goes */
+	return ecg_table_done(sc, st, ecg_segs_launch(v, sc->dev, st));
 }
 
 /* ---- sgl bookkeeping (daos_sgl_get_bytes with check_buf = true) -------- */

@@ -327,6 +327,115 @@ def test_two_calls_back_to_back_on_one_stream(ctx, ecglib, oracle):
 
 
 @gpu
+def test_different_table_users_hand_the_two_slots_to_each_other(ecglib, oracle):
+    """Two rounds of recover_masks_ptrs, csum_masked_ptrs, csum_cells_ptrs, matmul_ptrs, update_ptrs
+    and recover_masks_ptrs_csum on one stream of a fresh context with no sync in between: every call
+    takes the slot the call before last used.  csum_cells_ptrs brings a 72 000-byte table, above the
+    64 KiB a slot starts with, so its slot is re-allocated while the other still has a reader.  Each
+    call has its own buffers; every output is compared with the oracle after the one sync."""
+    k, p, C_, S_, cs, htype, NC = 4, 2, 4096, 5, 2048, 2, 9000
+    n, order = k + p, [3, 0, 4, 1, 2]
+    masks = seeded_masks(k, p, S_)                              # of the stripes; row r is stripe order[r]
+    rows = [masks[s] for s in order]
+    nbits = sum(bin(m).count("1") for m in masks)
+    cw, rnd = cm.codewords(oracle, k, p, C_, S_), cm.random_cells(k, p, C_, S_)
+    ref_cw = reference(oracle, ("cw", k, p, C_, S_), htype, cs, 1, cw)
+    ref_rnd = reference(oracle, ("rnd", k, p, C_, S_), htype, cs, 1, rnd)
+    small = np.random.default_rng(9000).integers(0, 256, (1, NC, 64), dtype=np.uint8)
+    ref_small = reference(oracle, ("small", NC), htype, cs, 1, small)
+    perm = np.random.default_rng(9001).permutation(NC)
+    en = oracle.cauchy1(k, p)[k:]
+    c2 = ecglib.Context(0)
+    held = []
+
+    def keep(b):
+        held.append(b)
+        return b
+
+    def one_round():
+        r = SimpleNamespace()
+        r.rec, r.clean = erased_rig(c2, oracle, k, p, C_, S_, masks)
+        r.msk, r.msums = PtrRig(c2, k, p, C_, rnd), Sums(c2, ref_rnd.shape)
+        r.cells, r.csums = c2.alloc(NC * 64), Sums(c2, ref_small.shape)
+        r.mm, r.upd = PtrRig(c2, k, p, C_, rnd), PtrRig(c2, k, p, C_, rnd)
+        r.both, _ = erased_rig(c2, oracle, k, p, C_, S_, masks)
+        r.bsums = Sums(c2, ref_cw.shape)
+        for b in vars(r).values():
+            if hasattr(b, "free"):
+                keep(b)
+        return r
+
+    def start(r):
+        load(r.rec, rows)
+        load(r.msk, rows, r.msums)
+        r.cells.upload(small.reshape(-1))
+        r.csums.reset()
+        for rig in (r.mm, r.upd):
+            rig.buf.upload(rig.img)
+        load(r.both, rows, r.bsums)
+
+    def calls(r):
+        c2.recover_masks_ptrs(k, p, C_, S_, r.rec.table(order), r.rec.masks.ptr, r.rec.result.ptr)
+        c2.csum_masked_ptrs(htype, cs, 1, k, p, C_, S_, r.msk.table(order), r.msk.masks.ptr, 3, r.msums.ptr,
+                            r.msk.result.ptr)
+        c2.csum_cells_ptrs(htype, cs, 1, 64, [r.cells.ptr + 64 * int(i) for i in perm], r.csums.ptr)
+        c2.matmul_ptrs(k, p, en, C_, S_, r.mm.table(order))
+        assert ecglib.last_kernel().startswith("ecg_mm_ptr_kernel<"), ecglib.last_kernel()
+        at = r.upd.buf.ptr + r.upd.off
+        c2.update_ptrs(k, p, C_, [(s % k, int(at[s, 0]), int(at[s, 1]), [int(a) for a in at[s, k:]]) for s in order])
+        composite(r)
+
+    def composite(r):
+        c2.recover_masks_ptrs_csum(k, p, C_, S_, r.both.table(order), r.both.masks.ptr, r.both.result.ptr, htype, cs,
+                                   1, r.bsums.ptr)
+
+    def check(r):
+        for rig in (r.rec, r.both):
+            same(rig.buf.download(), r.clean)
+            assert rig.words() == [S_, U64MAX, nbits, 0]
+        same(r.msk.buf.download(), r.msk.img)
+        assert r.msk.words() == words(rows, k, p, 3)
+        same(r.msums.buf.download(), r.msums.image(expect_array(ref_rnd[order], rows, k, p, 3,
+                                                                start=blank(ref_rnd.shape))))
+        same(r.cells.download(), small.reshape(-1))
+        same(r.csums.buf.download(), r.csums.image(ref_small[:, perm]))
+        want = r.mm.img.copy()
+        for s in range(S_):
+            for i, cell in enumerate(oracle.encode_data(en, rnd[s, :k])):
+                r.mm.cell(want, s, k + i)[:] = cell
+        same(r.mm.buf.download(), want)
+        want = r.upd.img.copy()
+        for s in range(S_):
+            for i, cell in enumerate(oracle.encode_data_update(en, s % k, rnd[s, 0] ^ rnd[s, 1], rnd[s, k:])):
+                r.upd.cell(want, s, k + i)[:] = cell
+        same(r.upd.buf.download(), want)
+        same(r.bsums.buf.download(), r.bsums.image(expect_array(ref_cw[order], rows, k, p, 1,
+                                                                start=blank(ref_cw.shape))))
+
+    try:
+        rounds = [one_round(), one_round()]
+        # the set table and the CRC tables are built, synchronously, on first use: not inside the sequence
+        # (one small table: both slots stay at their first 64 KiB)
+        start(rounds[0])
+        composite(rounds[0])
+        c2.sync()
+        for r in rounds:
+            start(r)
+        c2.sync()
+        for r in rounds:                                        # no sync in between
+            calls(r)
+        name = ecglib.last_kernel()
+        c2.sync()
+        assert name == ptr_kernel(htype, False), name           # a cell-table kernel: no affine route
+        for r in rounds:
+            check(r)
+    finally:
+        for b in held:
+            b.free()
+        c2.close()
+
+
+@gpu
 def test_table_argument_errors(ctx, ecglib):
     """What the host test cannot reach without a context: the table itself."""
     L = ecglib.lib()
