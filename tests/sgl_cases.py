@@ -12,7 +12,15 @@ from oracle import sgl_py
 
 
 def make_case(seed: int, k: int, e_len: int, iod_size: int, nstripes: int, n_iod: int, n_iov: int,
-              n_recov: int, zero_iovs: int = 0, slack: int = 0):
+              n_recov: int, zero_iovs: int = 0, slack: int = 0, *, on_boundary: bool = False,
+              short: float | None = None, zero_front: int = 0, zero_back: int = 0):
+    """The keyword arguments are applied to the iov capacities after everything else is drawn (they
+    draw nothing themselves, so the positional arguments alone give what they always gave), in
+    this order: on_boundary cuts an iov where a recovered record's bytes begin in the user's byte
+    stream (user_offsets; the first such offset that is neither 0 nor a boundary already), so a
+    fill-back copy starts exactly on an iov's end; short keeps only the first short * capacity
+    bytes of the sgl (at least one), so the copies run out of iovs; zero_front / zero_back put
+    empty iovs at the very front / back."""
     rng = np.random.default_rng(seed)
     srn = k * e_len
     nrec = nstripes * srn
@@ -45,8 +53,41 @@ def make_case(seed: int, k: int, e_len: int, iod_size: int, nstripes: int, n_iod
             hi_lim = iod[j + 1][0] + iod[j + 1][1]
         hi = lo + 1 + int(rng.integers(0, hi_lim - lo))
         recov.append({"idx": lo, "nr": hi - lo, "ep": int(rng.integers(1, 3)), "type": sgl_py.DRT_SHADOW})
-    return dict(k=k, e_len=e_len, iod_size=iod_size, srn=srn, content=content, iod=iod, lens=lens,
+    case = dict(k=k, e_len=e_len, iod_size=iod_size, srn=srn, content=content, iod=iod, lens=lens,
                 recov=recov)
+    if on_boundary:
+        ends = set(np.cumsum(lens).tolist())
+        for off in user_offsets(case):
+            if 0 < off < sum(lens) and off not in ends:
+                i = int(np.searchsorted(np.cumsum(lens), off, side="right"))
+                head = off - sum(lens[:i])
+                lens[i:i + 1] = [head, lens[i] - head]
+                break
+    if short is not None:
+        keep, out = max(1, int(short * sum(lens))), []
+        for n in lens:
+            out.append(min(n, keep))
+            keep -= out[-1]
+            if keep == 0:
+                break
+        lens[:] = out
+    lens[:0] = [0] * zero_front
+    lens += [0] * zero_back
+    return case
+
+
+def user_offsets(case):
+    """The byte offset in the user's stream (the iod recxs laid end to end) at which each piece of
+    a recovered recx begins: one piece per iod recx it overlaps."""
+    isz, out = case["iod_size"], []
+    for r in case["recov"]:
+        base = 0
+        for a, n in case["iod"]:
+            lo, hi = max(a, r["idx"]), min(a + n, r["idx"] + r["nr"])
+            if lo < hi:
+                out.append((base + lo - a) * isz)
+            base += n
+    return out
 
 
 def stripe_image(case, stripes, p, parity_fn=None):
@@ -64,12 +105,12 @@ def stripe_image(case, stripes, p, parity_fn=None):
     return np.concatenate(blocks) if blocks else np.zeros(0, np.uint8)
 
 
-def expected_user_bytes(case, fill=0xEE):
+def expected_user_bytes(case, fill=0xEE, size=None):
     """What the user's sgl should hold after fill-back: object bytes at the
     recovered records' iod offsets, `fill` elsewhere (as one flat array of
-    iov capacities)."""
+    iov capacities, or of `size` bytes: what an sgl of that capacity would hold)."""
     isz = case["iod_size"]
-    out = np.full(sum(case["lens"]), fill, np.uint8)
+    out = np.full(sum(case["lens"]) if size is None else size, fill, np.uint8)
     off = 0
     for a, n in case["iod"]:
         for r in case["recov"]:

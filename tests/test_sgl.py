@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 from oracle import sgl_py
-from tests.sgl_cases import expected_user_bytes, make_case, stripe_image
+from tests.sgl_cases import expected_user_bytes, make_case, stripe_image, user_offsets
 
 
 def c_stripe_list(ecglib, srn, items):
@@ -74,12 +74,38 @@ CASES = [  # seed, k, e_len, iod_size, nstripes, n_iod, n_iov, n_recov, zero_iov
 ]
 
 
-@pytest.mark.parametrize("case_args", CASES)
+KW_CASES = [  # the positional arguments, then make_case's keyword arguments
+    (21, 4, 64, 17, 6, 3, 300, 6, 0, 0, {}),                                    # iod_size 17, hundreds of iovs
+    (22, 2, 100, 3, 8, 4, 9, 6, 0, 0, {"zero_front": 2, "zero_back": 3}),       # empty iovs at the very front and back
+    (23, 8, 32, 8, 5, 2, 12, 5, 1, 0, {"on_boundary": True}),                   # a copy that starts on an iov's end
+    (24, 4, 64, 1, 6, 3, 5, 4, 0, 0, {"short": 0.5}),                           # an sgl shorter than the records
+    (25, 16, 16, 5, 4, 5, 120, 7, 3, 1, {"short": 0.03, "zero_front": 1, "zero_back": 1}),
+    (26, 4, 256, 17, 3, 2, 200, 8, 2, 0, {"short": 0.9, "on_boundary": True, "zero_back": 2}),
+]
+
+
+def test_kw_cases_are_what_they_say():
+    """The classes KW_CASES is there for, read off the cases."""
+    cases = [make_case(*a[:-1], **a[-1]) for a in KW_CASES]
+    assert [c["iod_size"] for c in cases] == [17, 3, 8, 1, 5, 17] and len(cases[0]["lens"]) >= 250
+    assert cases[1]["lens"][:2] == [0, 0] and cases[1]["lens"][-3:] == [0, 0, 0] and cases[1]["lens"][2] > 0
+    for c, kw in zip(cases, (a[-1] for a in KW_CASES)):
+        total = sum(n for _, n in c["iod"]) * c["iod_size"]
+        if "short" in kw:
+            assert 0 < sum(c["lens"]) < total and max(user_offsets(c)) > sum(c["lens"])   # a copy beyond the sgl
+        if "on_boundary" in kw:     # sgl_skip's equality branch: a copy's offset is an iov's end
+            ends = set(np.cumsum(c["lens"]).tolist())
+            assert any(0 < off and off in ends for off in user_offsets(c))
+
+
+@pytest.mark.parametrize("case_args", CASES + KW_CASES)
 def test_fill_back_oracle_semantics(case_args):
     """The restated fill-back puts exactly the recovered records' bytes at
     their user-sgl offsets, and keeps the reference's iov_len / sg_nr_out
-    bookkeeping within capacity."""
-    case = make_case(*case_args)
+    bookkeeping within capacity.  An sgl shorter than the records holds the
+    front of what a full one would: the copies take what fits."""
+    kw = case_args[-1] if isinstance(case_args[-1], dict) else {}
+    case = make_case(*[a for a in case_args if not isinstance(a, dict)], **kw)
     stripes = sgl_py.stripe_list_init(case["srn"], case["recov"])
     p = 2
     img = stripe_image(case, stripes, p)
@@ -88,7 +114,8 @@ def test_fill_back_oracle_semantics(case_args):
     sgl_py.recov_fill_back(case["iod_size"], case["iod"], sgl, case["recov"], stripes, img, (case["k"] + p) * C,
                            case["srn"])
     got = np.concatenate(sgl.bufs) if sgl.bufs else np.zeros(0, np.uint8)
-    assert np.array_equal(got, expected_user_bytes(case))
+    full = max(got.size, sum(n for _, n in case["iod"]) * case["iod_size"])
+    assert np.array_equal(got, expected_user_bytes(case, size=full)[:got.size])
     assert all(0 <= ln <= len(b) for ln, b in zip(sgl.iov_len, sgl.bufs))
     assert 0 < sgl.nr_out <= len(sgl.bufs)
 
