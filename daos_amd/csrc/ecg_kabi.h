@@ -310,6 +310,9 @@ static inline ECG_KABI_HD int ecg_verify_classify(uint32_t status, int k, int p)
 }
 
 #define ECG_KID_VERIFY 800u	/* verify kernel ids start here (below ECG_KID_COPY_SEGS) */
+#define ECG_KID_VERIFY_PTRS 836u	/* ids of the cell-table verify kernels (836 .. 849: the 13 lane kernels and
+					 * the byte kernel, above the cell-table recover_masks kernels' 820 .. 835,
+					 * below ECG_KID_REPAIR) */
 
 #ifdef __cplusplus
 extern "C" {
@@ -319,8 +322,16 @@ extern "C" {
  * host on `stream`.  bytewise = 0: the 16-byte lane kernel (every cell
  * address and stride 16-byte aligned, cell_bytes % 16 == 0); 1: the
  * byte-granular kernel (any alignment and length).  cfg: grid_x / grid_y and
- * wg_per_cu as for the product. */
-int ecg_k_launch_verify(const ecg_mm_params_t *p, uint32_t *status, int bytewise,
+ * wg_per_cu as for the product.
+ * cells_dev == NULL: the strided operands above.  Otherwise ecg_verify_ptrs:
+ * the same pass with the cells of stripe s at the addresses cells_dev[s * (k +
+ * rows) + c], c = 0 .. k-1 the data cells and k .. k+rows-1 the parity rows
+ * (device memory, read only for the launch); p->src / dst, the strides and the
+ * cell offsets are then unused, and bytewise is the host's lane choice, 0 only
+ * when EVERY table entry and cell_bytes are multiples of 16: the launcher does
+ * not read the table.  ecg_k_verify_kernel_name serves the ids of both
+ * layouts. */
+int ecg_k_launch_verify(const ecg_mm_params_t *p, const uint64_t *cells_dev, uint32_t *status, int bytewise,
 			const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
 /* result[0] += bad stripes, result[1] = min(result[1], lowest bad stripe),
  * result[2] += stripes ecg_verify_classify attributes to one cell, result[3]
@@ -343,12 +354,22 @@ const char *ecg_k_verify_kernel_name(uint32_t kernel_id);
  * 64 stripes (a block row reads its group's status words with one load) and
  * by default at most ECG_REPAIR_GRID_X blocks share a group and stride over
  * a stripe's 4 KiB columns, so a clean batch costs its block count, not its
- * bytes. */
+ * bytes.
+ * cells_dev == NULL: the strided operands above.  Otherwise ecg_repair_ptrs:
+ * the cells of stripe s at the addresses cells_dev[s * (k + p) + c] in logical
+ * cell order (device memory, read only for the launch), p->src / dst, the
+ * strides and the cell offsets unused: the sources of c >= k are the entries 0
+ * .. k-1, those of c < k the same with entry k in slot c, the destination
+ * entry c.  bytewise = 0 then only when EVERY table entry and cell_bytes are
+ * multiples of 16 (the host's check).  ecg_k_repair_kernel_name serves the ids
+ * of both layouts. */
 #define ECG_REPAIR_GRID_X 64u
-#define ECG_KID_REPAIR 850u	/* repair kernel ids start here (below ECG_KID_COPY_SEGS) */
-int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint32_t *status,
-			uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg, void *stream,
-			uint32_t *kernel_id);
+#define ECG_KID_REPAIR 850u	/* ids of the strided repair kernels start here (850 .. 855) */
+#define ECG_KID_REPAIR_PTRS 856u	/* ids of the cell-table repair kernels (856 .. 861: the 5 lane kernels and
+					 * the byte kernel, below ECG_KID_RECOVER_MASKS) */
+int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint64_t *cells_dev,
+			const uint32_t *status, uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg,
+			void *stream, uint32_t *kernel_id);
 const char *ecg_k_repair_kernel_name(uint32_t kernel_id);
 #ifdef __cplusplus
 }

@@ -178,7 +178,8 @@ int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t
 			    int64_t stripe_stride, const uint32_t *masks, const void *result, unsigned flags);
 /* what the cell-table calls share (ecg_recover_masks.c): ecg_recover_masks_ptrs
  * and, in ecg_csum.c, ecg_csum_masked_ptrs, ecg_csum_cells_ptrs and
- * ecg_recover_masks_ptrs_csum */
+ * ecg_recover_masks_ptrs_csum; ecg_verify_ptrs (ecg_verify.c), ecg_repair_ptrs
+ * and ecg_scrub_ptrs (ecg_repair.c) */
 /* a range no cell of a table may share a byte with; `what` names it in the error */
 struct ecg_clear {
 	const void *at;
@@ -213,6 +214,27 @@ int ecg_rm_settbl(ecg_ctx_t *ctx, int k, int p, const void **settbl);
 int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int p, uint64_t C, uint32_t S,
 		  void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
 		  const uint32_t *masks, void *result, unsigned flags, hipStream_t st);
+
+/* what the strided and the cell-table scrub calls share (ecg_verify.c):
+ * ecg_verify, ecg_repair, ecg_verify_ptrs, ecg_repair_ptrs, ecg_scrub_ptrs */
+/* zeroed launch parameters with the shape (k, rows = p, C, S) and, with
+ * `rows`, the Cauchy parity rows as perm tables and `accumulate`; free() it */
+int ecg_scrub_params(const char *fn, int k, int p, uint64_t C, uint32_t S, int rows, ecg_mm_params_t **out);
+/* the strided operands: data cells as sources, parity rows as destinations */
+void ecg_scrub_strided(ecg_mm_params_t *prm, const void *data, int64_t data_stripe_stride, const void *parity,
+		       int64_t parity_cell_stride, int64_t parity_stripe_stride);
+/* result = {0, UINT64_MAX, 0, 0} and, S != 0, every status word clean with
+ * every data cell a candidate, on st */
+int ecg_verify_preset(const char *fn, int k, uint32_t S, uint32_t *status, void *result, hipStream_t st);
+/* syndrome pass + summary over prm's strided operands, or with cells_dev over
+ * a staged cell table; counts 2 launches and names the syndrome kernel */
+int ecg_verify_launch(ecg_ctx_t *ctx, const char *fn, const ecg_mm_params_t *prm, const uint64_t *cells_dev,
+		      int bytewise, uint32_t *status, void *result, hipStream_t st);
+/* the device-free argument checks of the cell-table scrub calls in their
+ * documented order (r2: ecg_scrub_ptrs's repair_result, NULL for the others;
+ * have_ctx = 0 fails where they report a NULL context) */
+int ecg_scrub_ptrs_check(const char *fn, int have_ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+			 const uint32_t *status, const void *result, const void *const *r2);
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);

@@ -19,7 +19,16 @@
  * The (k + p) x k rows become perm tables once per (k, p) and context, in a
  * device buffer (7.5 KiB at most: too large for kernel arguments next to
  * ecg_mm_params_t).
+ *
+ * ecg_repair_ptrs is the same launch for stripes that are not one strided
+ * image (a host table of cell addresses, the cell-table kernels of the same
+ * file; a table that is a strided image after all is handed to ecg_repair),
+ * and ecg_scrub_ptrs the whole scrub over one such table: checked and staged
+ * once, the verify, its summary and the repair queued behind one upload.  The
+ * set-up they share with the strided calls is in ecg_verify.c
+ * (ecg_scrub_params, ecg_scrub_strided, ecg_verify_preset, ecg_verify_launch).
  */
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -71,17 +80,43 @@ static int build_rows(void *img, const void *arg)
 	return rc;
 }
 
+/* The row tables of (k, p), one per context: synchronous on first use.  Takes
+ * ctx->lock, so the cell-table calls fetch it before they lock their slot. */
+static int repair_rowtbl(ecg_ctx_t *ctx, int k, int p, const void **rowtbl)
+{
+	const int kp[2] = {k, p};
+
+	return ecg_ctx_kp_table(ctx, &ctx->repair_tbl[k - 1][p - 1], (size_t)(k + p) * k * sizeof(ecg_ptbl_t), build_rows,
+				kp, "repair tables", rowtbl);
+}
+
+/* The launch of every repair call (fn names it in the trace range and the
+ * messages): over prm's strided operands, or with cells_dev over a staged cell
+ * table. */
+static int repair_launch(ecg_ctx_t *ctx, const char *fn, const ecg_mm_params_t *prm, const void *rowtbl,
+			 const uint64_t *cells_dev, int bytewise, const uint32_t *status, void *result, hipStream_t st)
+{
+	char what[48];
+	uint32_t kid = 0;
+	int e;
+
+	snprintf(what, sizeof(what), "ecg:%s", fn);
+	ecg_trace_push(what);
+	e = ecg_k_launch_repair(prm, rowtbl, cells_dev, status, (uint64_t *)result, ctx->cfg.variant == 2 || bytewise,
+				&ctx->cfg, (void *)st, &kid);
+	snprintf(what, sizeof(what), "%s kernel launch", fn);
+	return ecg_launch_done(ctx, e, what, 1, ecg_k_repair_kernel_name(kid));
+}
+
 int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	       void *data, int64_t data_stripe_stride,
 	       void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
 	       const uint32_t *status, void *result, void *stream)
 {
-	const int kp[2] = {k, p};
 	const void *rowtbl = NULL;
 	ecg_mm_params_t *prm;
 	hipStream_t st;
-	uint32_t kid = 0;
-	int rc, e, r, j, bytewise;
+	int rc;
 
 	if (ctx == NULL)
 		return ecg_fail(-ECG_DER_INVAL, "repair: NULL context");
@@ -109,33 +144,128 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	if (rc || S == 0 || C == 0)
 		return rc;
 
-	/* the row tables of (k, p): synchronous on first use */
-	rc = ecg_ctx_kp_table(ctx, &ctx->repair_tbl[k - 1][p - 1], (size_t)(k + p) * k * sizeof(ecg_ptbl_t), build_rows,
-			      kp, "repair tables", &rowtbl);
+	rc = repair_rowtbl(ctx, k, p, &rowtbl);
+	if (rc == 0)
+		rc = ecg_scrub_params("repair", k, p, C, S, 0, &prm);
 	if (rc)
 		return rc;
-	prm = calloc(1, sizeof(*prm));
-	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "repair: calloc");
 	/* the operands of ecg_verify: data cells as sources, parity rows in the
 	 * destination slot; which of them a stripe reads and which one it
 	 * writes is the kernel's choice per stripe */
-	prm->src = data;
-	prm->dst = parity;
-	prm->src_stripe_stride = data_stripe_stride;
-	prm->dst_stripe_stride = parity_stripe_stride;
-	prm->cell_bytes = C;
-	prm->nstripes = S;
-	prm->k = (uint32_t)k;
-	prm->rows = (uint32_t)p;
-	for (j = 0; j < k; j++)
-		prm->src_cell_off[j] = (int64_t)j * (int64_t)C;
-	for (r = 0; r < p; r++)
-		prm->dst_cell_off[r] = (int64_t)r * parity_cell_stride;
-	bytewise = ctx->cfg.variant == 2 || ecg_k_align_granule(prm) != 16u || C % 16u;
-
-	ecg_trace_push("ecg:repair");
-	e = ecg_k_launch_repair(prm, rowtbl, status, (uint64_t *)result, bytewise, &ctx->cfg, (void *)st, &kid);
+	ecg_scrub_strided(prm, data, data_stripe_stride, parity, parity_cell_stride, parity_stripe_stride);
+	rc = repair_launch(ctx, "repair", prm, rowtbl, NULL, ecg_k_align_granule(prm) != 16u || C % 16u, status, result,
+			   st);
 	free(prm);
-	return ecg_launch_done(ctx, e, "repair kernel launch", 1, ecg_k_repair_kernel_name(kid));
+	return rc;
+}
+
+/* Is the staged table one strided image [S][k+p][C] whose arguments pass
+ * ecg_repair's own checks (status clear of the whole image, gaps included)? */
+static int repair_affine(const struct ecg_staged *t, void *const *cells, int k, int p, uint64_t C, uint32_t S,
+			 const uint32_t *status)
+{
+	return t->affine && !ecg_cells_overlap(status, 4ull * S, cells[0], S, t->stride, k + p, (int64_t)C, C);
+}
+
+int ecg_repair_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells, const uint32_t *status,
+		    void *result, void *stream)
+{
+	static const char fn[] = "repair_ptrs";
+	/* the kernel reads status words and counts into result while other
+	 * blocks write cells */
+	const struct ecg_clear clear[2] = {{status, 4ull * S, "status"}, {result, 32, "result"}};
+	const void *rowtbl = NULL;
+	ecg_mm_params_t *prm;
+	struct ecg_staged t;
+	hipStream_t st;
+	int rc;
+
+	rc = ecg_scrub_ptrs_check(fn, ctx != NULL, k, p, C, S, cells, status, result, NULL);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing repaired, nothing left */
+		return ecg_result_reset(result, st, "repair_ptrs memset");
+
+	rc = repair_rowtbl(ctx, k, p, &rowtbl);	/* takes the lock: before open */
+	if (rc == 0)
+		rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(k + p), C, clear, 2, &t);
+	if (rc)
+		return rc;
+	/* ecg_repair's own layout: its launch, with no table and no dependent
+	 * address loads */
+	if (repair_affine(&t, cells, k, p, C, S, status)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_repair(ctx, k, p, C, S, cells[0], t.stride, (uint8_t *)cells[0] + (uint64_t)k * C, (int64_t)C,
+				  t.stride, status, result, stream);
+	}
+	rc = ecg_scrub_params(fn, k, p, C, S, 0, &prm);
+	if (rc)
+		return ecg_staged_close(ctx, &t, st, rc);
+	rc = ecg_staged_upload(&t, result, st, "repair_ptrs memset", "repair_ptrs cell table");
+	if (rc == 0)
+		rc = repair_launch(ctx, fn, prm, rowtbl, t.sc->dev, (t.bits | C) % 16u != 0, status, result, st);
+	free(prm);
+	return ecg_staged_close(ctx, &t, st, rc);
+}
+
+int ecg_scrub_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells, uint32_t *status,
+		   void *verify_result, void *repair_result, void *stream)
+{
+	static const char fn[] = "scrub_ptrs";
+	const struct ecg_clear clear[3] = {{status, 4ull * S, "status"},
+					   {verify_result, 32, "verify_result"},
+					   {repair_result, 32, "repair_result"}};
+	const void *rr = repair_result;
+	const void *rowtbl = NULL;
+	ecg_mm_params_t *prm;
+	struct ecg_staged t;
+	hipStream_t st;
+	int rc, bytewise;
+
+	rc = ecg_scrub_ptrs_check(fn, ctx != NULL, k, p, C, S, cells, status, verify_result, &rr);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0) {	/* the empty batches of both calls */
+		rc = ecg_verify_preset(fn, k, S, status, verify_result, st);
+		return rc ? rc : ecg_result_reset(repair_result, st, "scrub_ptrs memset");
+	}
+
+	rc = repair_rowtbl(ctx, k, p, &rowtbl);	/* takes the lock: before open */
+	if (rc == 0)
+		rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(k + p), C, clear, 3, &t);
+	if (rc)
+		return rc;
+	/* the strided calls' own layout, for both halves or for neither */
+	if (repair_affine(&t, cells, k, p, C, S, status)) {
+		void *par = (uint8_t *)cells[0] + (uint64_t)k * C;
+
+		ecg_staged_close(ctx, &t, st, 0);
+		rc = ecg_verify(ctx, k, p, C, S, cells[0], t.stride, par, (int64_t)C, t.stride, status, verify_result,
+				stream);
+		return rc ? rc : ecg_repair(ctx, k, p, C, S, cells[0], t.stride, par, (int64_t)C, t.stride, status,
+					    repair_result, stream);
+	}
+	/* one table, one upload; verify, summary and repair queued behind it
+	 * (the repair reads no tables from prm: the verify's serve both) */
+	rc = ecg_scrub_params(fn, k, p, C, S, 1, &prm);
+	if (rc)
+		return ecg_staged_close(ctx, &t, st, rc);
+	bytewise = (t.bits | C) % 16u != 0;
+	rc = ecg_verify_preset(fn, k, S, status, verify_result, st);
+	if (rc == 0)
+		rc = ecg_staged_upload(&t, repair_result, st, "scrub_ptrs memset", "scrub_ptrs cell table");
+	if (rc == 0)
+		rc = ecg_verify_launch(ctx, fn, prm, t.sc->dev, bytewise, status, verify_result, st);
+	if (rc == 0)
+		rc = repair_launch(ctx, fn, prm, rowtbl, t.sc->dev, bytewise, status, repair_result, st);
+	free(prm);
+	return ecg_staged_close(ctx, &t, st, rc);
 }

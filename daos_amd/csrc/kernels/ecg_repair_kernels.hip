@@ -28,6 +28,15 @@
 // size, and a bad stripe still has ECG_REPAIR_GRID_X blocks to itself.
 // Column-block 0 of a group counts its bad stripes into `result`
 // (ecg_rows_dev.h rows_count).
+//
+// Two layouts, one body each for the lane and the byte kernels (rp_lanes,
+// rp_bytes): the strided operands of ecg_verify, or a table of cell addresses,
+// cells[s * (k + p) + c] = the device address of logical cell c of stripe s
+// (ecg_repair_ptrs).  The bodies ask an addressing struct (rp_strided,
+// rp_table) where a stripe's cells are and share everything else; the four
+// __global__ entry points only choose it.  Over a table a stripe's sources are
+// pt[j], pt[k] in slot c when a data cell is rewritten, and its destination
+// pt[c]: indices inside the stripe's table row for any status value.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -52,20 +61,57 @@ struct repair_read {
 	__device__ unsigned long long units(int c) const { return c < k; }
 };
 
-} // namespace
+// Where a stripe's cells are -- all the strided and the cell-table kernels
+// differ in (as ecg_recover_masks_kernels.hip rm_strided / rm_table).  A body
+// positions the struct on a stripe (at) and asks for the address of data cell
+// j (src), of parity row 0 (par0) and of the located cell c (dst); c is always
+// the classified cell, 0 .. k+p-1.  The launch parameters are handed to each
+// of them, not kept in the struct.
 
-// K as ecg_mm_kernel's (0 = runtime-shaped), one output row.  16-byte lanes
-// only: every cell address and stride 16-byte aligned, C % 16 == 0 (the
-// launcher sends everything else to the byte kernel), so a partial last
-// column is a lane mask.  P as ecg_verify's: src the data cells, dst the
-// parity rows (dst_cell_off[r] = r * parity_cell_stride), rows = p.
-template <int K>
-__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, 1, 16) ? ECG_MM_WPE(K, 1, 16) : 1)
-ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
-		  const uint32_t *__restrict__ status, unsigned long long *result)
+// P as ecg_verify's: src the data cells, dst the parity rows (dst_cell_off[r]
+// = r * parity_cell_stride)
+struct rp_strided {
+	uint64_t sb, pb;
+
+	__device__ void at(const ecg_mm_params_t &P, uint32_t s)
+	{
+		sb = (uint64_t)(uintptr_t)P.src + (uint64_t)((int64_t)s * P.src_stripe_stride);
+		pb = (uint64_t)(uintptr_t)P.dst + (uint64_t)((int64_t)s * P.dst_stripe_stride);
+	}
+	__device__ uint64_t src(const ecg_mm_params_t &P, int j) const { return sb + (uint64_t)P.src_cell_off[j]; }
+	__device__ uint64_t par0(const ecg_mm_params_t &P) const { return pb + (uint64_t)P.dst_cell_off[0]; }
+	__device__ uint64_t dst(const ecg_mm_params_t &P, int c, int k) const
+	{
+		return c < k ? sb + (uint64_t)c * P.cell_bytes : pb + (uint64_t)P.dst_cell_off[c - k];
+	}
+};
+
+// The stripe's row pt of a cell table: pt[c] the address of logical cell c
+// (wave-uniform: c comes from a readlane, so these are scalar loads of a
+// read-only table), loaded once per stripe, before the column loop.
+struct rp_table {
+	const uint64_t *__restrict__ cells;
+	uint32_t k, n;	// data cells, k + p
+	const uint64_t *__restrict__ pt;
+
+	__device__ rp_table(const uint64_t *cells_, uint32_t k_, uint32_t p_) : cells(cells_), k(k_), n(k_ + p_) {}
+	__device__ void at(const ecg_mm_params_t &, uint32_t s) { pt = cells + (uint64_t)s * n; }
+	__device__ uint64_t src(const ecg_mm_params_t &, int j) const { return pt[j]; }
+	__device__ uint64_t par0(const ecg_mm_params_t &) const { return pt[k]; }
+	__device__ uint64_t dst(const ecg_mm_params_t &, int c, int) const { return pt[c]; }
+};
+
+// The lane kernels' body.  K as ecg_mm_kernel's (0 = runtime-shaped), one
+// output row.  16-byte lanes only: every cell address (and stride) 16-byte
+// aligned, C % 16 == 0 (the launcher sends everything else to the byte
+// kernel), so a partial last column is a lane mask.  s_tbl: the block's
+// ECG_TBL_WORDS(KM, 1) staged table words.  (No __restrict__ on the body's
+// pointers: the kernels' own arguments carry it.)
+template <int K, class Addr>
+__device__ __forceinline__ void rp_lanes(const ecg_mm_params_t &P, u32x4 *s_tbl, const ecg_ptbl_t *rowtbl,
+					 const uint32_t *status, unsigned long long *result, Addr A)
 {
 	constexpr int KM = K ? K : ECG_KMAX_K;
-	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, 1)];	// one output row
 	const int k = K ? K : (int)P.k;
 	const int p = (int)P.rows;
 	const uint64_t C = P.cell_bytes;
@@ -97,16 +143,15 @@ ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl
 			}
 
 			// the stripe's k sources and its destination (wave-uniform)
-			const uint64_t sb = (uint64_t)(uintptr_t)P.src + (uint64_t)((int64_t)s * P.src_stripe_stride);
-			const uint64_t pb = (uint64_t)(uintptr_t)P.dst + (uint64_t)((int64_t)s * P.dst_stripe_stride);
-			const uint64_t par0 = pb + (uint64_t)P.dst_cell_off[0];
+			A.at(P, s);
+			const uint64_t par0 = A.par0(P);
 			uint64_t base[KM + 1];
 
 #pragma unroll
 			for (int j = 0; j < KM; j++)
 				if (j < k)
-					base[j] = j == c ? par0 : sb + (uint64_t)P.src_cell_off[j];
-			base[KM] = c < k ? sb + (uint64_t)c * C : pb + (uint64_t)P.dst_cell_off[c - k];
+					base[j] = j == c ? par0 : A.src(P, j);
+			base[KM] = A.dst(P, c, k);
 
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
@@ -130,13 +175,13 @@ ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl
 	}
 }
 
-// Any alignment, any length: a block takes 4 KiB columns of one stripe at a
-// time, a lane the bytes t, t + 256, ... of a column.  Same status scan,
-// operands, rows and counters as the lane kernel; the row's tables are read
-// where they lie (wave-uniform loads).
-__global__ void __launch_bounds__(BLOCK)
-ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
-		       const uint32_t *__restrict__ status, unsigned long long *result)
+// The byte kernels' body.  Any alignment, any length: a block takes 4 KiB
+// columns of one stripe at a time, a lane the bytes t, t + 256, ... of a
+// column.  Same status scan, operands, rows and counters as the lane body;
+// the row's tables are read where they lie (wave-uniform loads).
+template <class Addr>
+__device__ __forceinline__ void rp_bytes(const ecg_mm_params_t &P, const ecg_ptbl_t *rowtbl, const uint32_t *status,
+					 unsigned long long *result, Addr A)
 {
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
@@ -150,11 +195,11 @@ ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ r
 
 		while (todo) {
 			const uint32_t s = rows_next(&todo, g, 64u, cl, &c);
-			const uint8_t *sb = P.src + (int64_t)s * P.src_stripe_stride;
-			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
-			const uint8_t *par0 = pb + P.dst_cell_off[0];
+
+			A.at(P, s);
+			const uint8_t *par0 = reinterpret_cast<const uint8_t *>((uintptr_t)A.par0(P));
 			const ecg_ptbl_t *row = rowtbl + c * k;
-			uint8_t *dst = c < k ? const_cast<uint8_t *>(sb) + (uint64_t)c * C : pb + P.dst_cell_off[c - k];
+			uint8_t *dst = reinterpret_cast<uint8_t *>((uintptr_t)A.dst(P, c, k));
 
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
@@ -163,7 +208,8 @@ ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ r
 					uint32_t o = 0;
 
 					for (int j = 0; j < k; j++) {
-						const uint8_t *src = j == c ? par0 : sb + P.src_cell_off[j];
+						const uint8_t *src =
+							j == c ? par0 : reinterpret_cast<const uint8_t *>((uintptr_t)A.src(P, j));
 
 						o ^= gf_mul1(row[j], src[i]);
 					}
@@ -174,23 +220,73 @@ ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ r
 	}
 }
 
+} // namespace
+
+// The entry points: the strided operands of P as ecg_verify's (ecg_repair),
+// or the table `cells` (ecg_repair_ptrs).
+template <int K>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, 1, 16) ? ECG_MM_WPE(K, 1, 16) : 1)
+ecg_repair_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+		  const uint32_t *__restrict__ status, unsigned long long *result)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(K ? K : ECG_KMAX_K, 1)];	// one output row
+
+	rp_lanes<K>(P, s_tbl, rowtbl, status, result, rp_strided());
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_repair_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+		       const uint32_t *__restrict__ status, unsigned long long *result)
+{
+	rp_bytes(P, rowtbl, status, result, rp_strided());
+}
+
+template <int K>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, 1, 16) ? ECG_MM_WPE(K, 1, 16) : 1)
+ecg_repair_ptr_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+		      const uint64_t *__restrict__ cells, const uint32_t *__restrict__ status,
+		      unsigned long long *result)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(K ? K : ECG_KMAX_K, 1)];
+
+	rp_lanes<K>(P, s_tbl, rowtbl, status, result, rp_table(cells, (uint32_t)(K ? K : (int)P.k), P.rows));
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_repair_ptr_byte_kernel(const ecg_mm_params_t P, const ecg_ptbl_t *__restrict__ rowtbl,
+			   const uint64_t *__restrict__ cells, const uint32_t *__restrict__ status,
+			   unsigned long long *result)
+{
+	rp_bytes(P, rowtbl, status, result, rp_table(cells, P.k, P.rows));
+}
+
 // ---------------------------------------------------------------------------
 // Dispatch
 // ---------------------------------------------------------------------------
 typedef void (*repair_fn_t)(const ecg_mm_params_t, const ecg_ptbl_t *, const uint32_t *, unsigned long long *);
+typedef void (*repair_pfn_t)(const ecg_mm_params_t, const ecg_ptbl_t *, const uint64_t *, const uint32_t *,
+			     unsigned long long *);
 
+// one table for both layouts: an entry's index is its kernel id above
+// ECG_KID_REPAIR (strided) or ECG_KID_REPAIR_PTRS (cell table)
 struct rentry {
 	int k;
 	repair_fn_t fn;
-	const char *name;
+	repair_pfn_t pfn;
+	const char *name, *pname;
 };
 
-#define RE(K_) {K_, ecg_repair_kernel<K_>, "ecg_repair_kernel<" #K_ ">"}
+#define RE(K_) {K_, ecg_repair_kernel<K_>, ecg_repair_ptr_kernel<K_>, "ecg_repair_kernel<" #K_ ">", \
+		"ecg_repair_ptr_kernel<" #K_ ">"}
 
 // the k of the DAOS EC classes; the rest runtime-shaped
 static const rentry g_repair[] = {RE(2), RE(4), RE(8), RE(16), RE(0)};
 #define N_REPAIR ((uint32_t)(sizeof(g_repair) / sizeof(g_repair[0])))
 #define KID_REPAIR_BYTE (ECG_KID_REPAIR + N_REPAIR)
+#define KID_REPAIR_PTR_BYTE (ECG_KID_REPAIR_PTRS + N_REPAIR)
+static_assert(ECG_KID_REPAIR + N_REPAIR + 1 <= ECG_KID_REPAIR_PTRS &&
+		      ECG_KID_REPAIR_PTRS + N_REPAIR + 1 <= ECG_KID_RECOVER_MASKS,
+	      "repair ids: 850 .. 855 strided, 856 .. 861 cell table");
 
 extern "C" const char *ecg_k_repair_kernel_name(uint32_t id)
 {
@@ -198,12 +294,16 @@ extern "C" const char *ecg_k_repair_kernel_name(uint32_t id)
 		return g_repair[id - ECG_KID_REPAIR].name;
 	if (id == KID_REPAIR_BYTE)
 		return "ecg_repair_byte_kernel";
+	if (id >= ECG_KID_REPAIR_PTRS && id < ECG_KID_REPAIR_PTRS + N_REPAIR)
+		return g_repair[id - ECG_KID_REPAIR_PTRS].pname;
+	if (id == KID_REPAIR_PTR_BYTE)
+		return "ecg_repair_ptr_byte_kernel";
 	return "?";
 }
 
-extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint32_t *status,
-				   uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg, void *stream,
-				   uint32_t *kernel_id)
+extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint64_t *cells_dev,
+				   const uint32_t *status, uint64_t *result, int bytewise,
+				   const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
 	uint32_t gx, gy;
@@ -216,14 +316,20 @@ extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *r
 	rows_grid(p, 64u, ECG_REPAIR_GRID_X, cfg, &gx, &gy);
 
 	if (bytewise) {
-		hipLaunchKernelGGL(ecg_repair_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
-				   (unsigned long long *)result);
+		if (cells_dev == nullptr)
+			hipLaunchKernelGGL(ecg_repair_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
+					   (unsigned long long *)result);
+		else
+			hipLaunchKernelGGL(ecg_repair_ptr_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl,
+					   cells_dev, status, (unsigned long long *)result);
 		if (kernel_id)
-			*kernel_id = KID_REPAIR_BYTE;
+			*kernel_id = cells_dev ? KID_REPAIR_PTR_BYTE : KID_REPAIR_BYTE;
 		return (int)hipGetLastError();
 	}
-	// the lane kernel reads and writes dwordx4 at the cells' own addresses
-	if (!aligned16(p) || p->cell_bytes % 16u)
+	// the lane kernels read and write dwordx4 at the cells' own addresses;
+	// those of a cell table the host has found 16-byte aligned (the table is
+	// not read here)
+	if ((cells_dev == nullptr && !aligned16(p)) || p->cell_bytes % 16u)
 		return (int)hipErrorInvalidValue;
 
 	uint32_t id = N_REPAIR - 1;	// <0>
@@ -232,9 +338,13 @@ extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *r
 			id = i;
 			break;
 		}
-	hipLaunchKernelGGL(g_repair[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
-			   (unsigned long long *)result);
+	if (cells_dev == nullptr)
+		hipLaunchKernelGGL(g_repair[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
+				   (unsigned long long *)result);
+	else
+		hipLaunchKernelGGL(g_repair[id].pfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, cells_dev, status,
+				   (unsigned long long *)result);
 	if (kernel_id)
-		*kernel_id = ECG_KID_REPAIR + id;
+		*kernel_id = (cells_dev ? ECG_KID_REPAIR_PTRS : ECG_KID_REPAIR) + id;
 	return (int)hipGetLastError();
 }

@@ -67,6 +67,9 @@ _SIGS = [
     ("ecg_repair", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_repair_row", C.c_int, [C.c_int, C.c_int, C.c_int, u8p, u32p]),
+    ("ecg_verify_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp, vp]),
+    ("ecg_repair_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp, vp]),
+    ("ecg_scrub_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp, vp, vp]),
     ("ecg_recover_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, vp, C.c_uint,
                                     vp]),
     ("ecg_recover_masks_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
@@ -662,6 +665,28 @@ class Context:
         left).  Queued behind verify() on the same stream it needs no sync in between."""
         _chk(lib().ecg_repair(self.h, k, p, cell_bytes, nstripes, data, data_stripe_stride, parity,
                               parity_cell_stride, parity_stripe_stride, status, result, stream), "repair")
+
+    def verify_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None, status: int,
+                    result: int, stream=None):
+        """ecg_verify_ptrs: verify() over a table of cell addresses -- cells[s*(k+p)+c]: device
+        address of logical cell c of stripe s (0..k-1 data, k..k+p-1 parity), as
+        recover_masks_ptrs() takes it; status and result as verify()'s."""
+        _chk(lib().ecg_verify_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), status, result,
+                                   stream), "verify_ptrs")
+
+    def repair_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None, status: int,
+                    result: int, stream=None):
+        """ecg_repair_ptrs: repair() over the table of cell addresses verify_ptrs() read; status:
+        the words it left (read only), result as repair()'s."""
+        _chk(lib().ecg_repair_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), status, result,
+                                   stream), "repair_ptrs")
+
+    def scrub_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None, status: int,
+                   verify_result: int, repair_result: int, stream=None):
+        """ecg_scrub_ptrs: verify_ptrs() then repair_ptrs() on one stream, the table checked and
+        staged once; verify_result / repair_result: the two calls' result words."""
+        _chk(lib().ecg_scrub_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), status,
+                                  verify_result, repair_result, stream), "scrub_ptrs")
 
     def recover_masks(self, k: int, p: int, cell_bytes: int, nstripes: int, stripes: int, stripe_stride: int,
                       masks: int, result: int, flags: int = 0, stream=None):

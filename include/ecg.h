@@ -316,6 +316,62 @@ int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstri
  * -ECG_DER_INVAL outside 0..k+p-1 or k/p out of range (k <= 16, p <= 8). */
 int ecg_repair_row(int k, int p, int cell, unsigned char *coef, uint32_t *src_idx);
 
+/* ecg_verify and ecg_repair over a TABLE OF CELL ADDRESSES, for callers whose
+ * stripes are not one strided image -- the object verify path fetches every
+ * shard of a stripe into a buffer of its own (ref:src/object/obj_verify.c).
+ * cells is exactly the table of ecg_recover_masks_ptrs (below): a HOST array of
+ * nstripes * (k+p) device addresses, cells[s*(k+p) + c] logical cell c of
+ * stripe s (0..k-1 data, k..k+p-1 parity), cell_bytes long, at any address.
+ * One table serves the whole scrub.  It is staged internally, so the caller
+ * may overwrite or free it as soon as the call returns.  k <= 16, p <= 8.
+ * status and result mean, word for word, what ecg_verify / ecg_repair define;
+ * stripe s gives exactly what those calls give for a contiguous copy of that
+ * stripe.  ecg_verify_ptrs writes nothing into any cell (aliased entries are
+ * harmless for it).  ecg_repair_ptrs writes only the one located cell c of
+ * each attributable stripe, the bytes ecg_recover(err_list = {c}) would write:
+ * for a data cell from cells[s][j], j != c, and cells[s][k]; for a parity cell
+ * from the k data cells.  Any status value is safe: every index into a
+ * stripe's table row comes from the classified cell (ecg_verify_cell), never
+ * from raw status bits.  nstripes == 0 leaves result {0, UINT64_MAX, 0, 0};
+ * cell_bytes == 0 in addition presets the status words (ecg_verify_ptrs), as
+ * the strided calls do.
+ * ecg_scrub_ptrs is ecg_verify_ptrs then ecg_repair_ptrs on one stream, with
+ * one pass over the table and one upload; verify_result and repair_result are
+ * the two calls' result words (two different addresses).
+ * -ECG_DER_INVAL, the message prefixed by the call's name, checked in this
+ * order: the k / p limits; result NULL or not 8-byte aligned (ecg_scrub_ptrs:
+ * verify_result, then repair_result, then the two being the same address);
+ * status NULL or not 4-byte aligned (nstripes != 0); a NULL context; cells NULL
+ * (nstripes and cell_bytes != 0); a NULL entry (the message names its index);
+ * status (4 * nstripes bytes) or a result (32 bytes) sharing a byte with a
+ * cell ("overlaps").
+ * NOT CHECKED, THE CALLER'S CONTRACT: NO CELL ecg_repair_ptrs WRITES (THE
+ * LOCATED CELL OF AN ATTRIBUTABLE STRIPE) MAY OVERLAP ANY OTHER CELL THE LAUNCH
+ * READS OR WRITES, AND EVERY CELL IS MEMORY OF THE CONTEXT'S DEVICE.
+ * A table in which cells[s*(k+p)+c] == cells[0] + s*stride + c*cell_bytes for
+ * one stride (one stripe whose cells are cell_bytes apart is always such a
+ * table), and whose arguments pass the strided call's own checks, IS the call
+ * ecg_verify(data = cells[0], stride, parity = cells[0] + k*cell_bytes,
+ * cell_bytes, stride) / ecg_repair of the same operands: no table is uploaded
+ * and ecg_last_kernel names that kernel (ecg_repair demands status clear of
+ * the whole image, gaps included; ecg_scrub_ptrs takes one route for both
+ * halves, by that demand).  Any other table runs ecg_verify_ptr_kernel<K,P> /
+ * ecg_repair_ptr_kernel<K> (16-byte lanes) when every entry and cell_bytes are
+ * multiples of 16, and ecg_verify_ptr_byte_kernel / ecg_repair_ptr_byte_kernel
+ * for the WHOLE launch when one is not, or with ecg_set_launch variant 2.
+ * Asynchronous on `stream`.  Telemetry: `launches` counts 2 for
+ * ecg_verify_ptrs (syndrome pass + summary), 1 for ecg_repair_ptrs and 3 for
+ * ecg_scrub_ptrs; ecg_last_kernel names the syndrome kernel after
+ * ecg_verify_ptrs and the repair kernel after the other two.  The caveats are
+ * ecg_verify's and ecg_repair's: location ASSUMES ONE WRONG CELL PER STRIPE. */
+int ecg_verify_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		    void *const *cells, uint32_t *status, void *result, void *stream);
+int ecg_repair_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		    void *const *cells, const uint32_t *status, void *result, void *stream);
+int ecg_scrub_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		   void *const *cells, uint32_t *status, void *verify_result, void *repair_result,
+		   void *stream);
+
 /* Recovery with one erasure set PER STRIPE, in one launch: a rebuild or
  * degraded-read batch whose stripes lost different shards, and the second
  * half of a checksum-driven scrub (ecg_csum.h: ecg_csum_extents ->

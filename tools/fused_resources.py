@@ -9,12 +9,13 @@ report`).  Needs no GPU.
       a SRC instantiation; SGPRs spilled into VGPR lanes are listed, they
       use no scratch)
   python tools/fused_resources.py --verify VERIFY.txt [PRODUCT.txt]
-      the ecg_verify kernels (remarks of ecg_verify_kernels.hip), each lane
-      kernel beside its product counterpart from the remarks of
-      ecg_kernels.hip; exit 1 if one uses scratch
+      the ecg_verify kernels, strided and cell-table (ptr) alike (remarks of
+      ecg_verify_kernels.hip), each ptr lane kernel below its strided
+      counterpart and each lane kernel beside its product counterpart from
+      the remarks of ecg_kernels.hip; exit 1 if one uses scratch
   python tools/fused_resources.py --repair REPAIR.txt [NEW.txt BASE.txt]...
-      the ecg_repair kernels (remarks of ecg_repair_kernels.hip); exit 1 if
-      one uses scratch.  Each NEW BASE pair after it: the remarks of one
+      the ecg_repair kernels, strided and cell-table (ptr) alike (remarks of
+      ecg_repair_kernels.hip); exit 1 if one uses scratch.  Each NEW BASE pair after it: the remarks of one
       other kernel file from this tree and from the tree before, every
       kernel of which must show identical figures (mm_ptr_item moved into
       ecg_mm_dev.h; exit 1 on any difference)
@@ -71,7 +72,7 @@ def parse(path):
     return out
 
 
-VERIFY = re.compile(r"_Z\d+(ecg_verify_(?:byte_|summary_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
+VERIFY = re.compile(r"_Z\d+(ecg_verify_(?:ptr_)?(?:byte_|summary_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
 PRODUCT = re.compile(r"_Z13ecg_mm_kernelILi(\d+)ELi(\d+)ELb0ELb0ELi16EE")
 
 
@@ -107,7 +108,8 @@ def verify_table(verify_txt, product_txt=None):
     extra = " product VGPRs | product waves/SIMD |" if prod else ""
     print("| kernel | " + " | ".join(FIELDS) + " |" + extra)
     print("|" + "---|" * (1 + len(FIELDS) + (2 if prod else 0)))
-    for key in sorted(ver, key=lambda t: (t[0] != "ecg_verify_kernel", t[0], t[1] == 0, t[1], t[2])):
+    # each cell-table (ptr) lane kernel right below its strided counterpart
+    for key in sorted(ver, key=lambda t: (t[1] < 0, t[0] if t[1] < 0 else "", t[1] == 0, t[1], t[2], "ptr" in t[0])):
         name, k, r = key
         v = ver[key]
         label = f"`{name}<{k},{r}>`" if k >= 0 else f"`{name}`"
@@ -123,7 +125,7 @@ def verify_table(verify_txt, product_txt=None):
     return bad
 
 
-REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
+REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
 UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 ANY = re.compile(r"(\S+)()()")
@@ -137,7 +139,7 @@ def repair_table(repair_txt, *pairs, pattern=REPAIR, what="repair"):
     bad = 0
     print("| kernel | " + " | ".join(FIELDS) + " |")
     print("|" + "---|" * (1 + len(FIELDS)))
-    for key in sorted(rep, key=lambda t: ("byte" in t[0], t[1] == 0, t[1], t[2])):
+    for key in sorted(rep, key=lambda t: ("byte" in t[0], t[1] == 0, t[1], t[2], t[0])):
         name, k, r = key
         v = rep[key]
         label = f"`{name}<{k}>`" if k >= 0 else f"`{name}`"
