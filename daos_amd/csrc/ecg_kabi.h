@@ -582,11 +582,22 @@ const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
  * the byte-granular kernel.  Block rows of `grp` stripes and the two grids as
  * ecg_k_launch_recover_masks (sparse = 0: ECG_RM_DENSE_GRP and up to
  * ECG_RM_DENSE_GRID_X column blocks; 1: 64 and ECG_REPAIR_GRID_X); cfg:
- * grid_x / grid_y override either. */
-#define ECG_KID_UPDATE_MASKS 890u	/* ids of the update_masks kernels start here (below ECG_KID_COPY_SEGS) */
-int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint32_t *masks, uint64_t *result, int packed,
-			      int bytewise, int sparse, const ecg_launch_cfg_t *cfg, void *stream,
-			      uint32_t *kernel_id);
+ * grid_x / grid_y override either.
+ * cells_dev == NULL: the strided operands above.  Otherwise
+ * ecg_update_masks_ptrs: the same update with the cells of stripe s at the
+ * addresses cells_dev[s * (2k + p) + c] -- c < k old cell c, k <= c < 2k new
+ * cell c - k, 2k <= c parity row c - 2k (device memory, read only for the
+ * launch); p->src / src2 / dst, the strides and dst_cell_off are then unused
+ * and `packed` must be 0 (hipErrorInvalidValue).  bytewise = 0 over a table:
+ * EVERY table entry 16-byte aligned (the host's check: the launcher does not
+ * read the table) and cell_bytes % 16 == 0.
+ * ecg_k_update_masks_kernel_name serves the ids of both layouts. */
+#define ECG_KID_UPDATE_MASKS 890u	/* ids of the strided update_masks kernels start here (890 .. 894) */
+#define ECG_KID_UPDATE_MASKS_PTRS 895u	/* ids of the cell-table update_masks kernels (895 .. 899: the 4 lane
+					 * kernels and the byte kernel, below ECG_KID_COPY_SEGS) */
+int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+			      uint64_t *result, int packed, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
+			      void *stream, uint32_t *kernel_id);
 const char *ecg_k_update_masks_kernel_name(uint32_t kernel_id);
 /* ecg_csum_mask (kernels/ecg_csum_kernels.hip): masks[s] |= 1u << (first_cell
  * + i) when any of the nch checksums of len (2, 4 or 8) bytes at index

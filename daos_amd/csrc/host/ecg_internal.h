@@ -179,7 +179,8 @@ int ecg_recover_masks_check(const char *fn, int have_ctx, int k, int p, uint64_t
 /* what the cell-table calls share (ecg_recover_masks.c): ecg_recover_masks_ptrs
  * and, in ecg_csum.c, ecg_csum_masked_ptrs, ecg_csum_cells_ptrs and
  * ecg_recover_masks_ptrs_csum; ecg_verify_ptrs (ecg_verify.c), ecg_repair_ptrs
- * and ecg_scrub_ptrs (ecg_repair.c) */
+ * and ecg_scrub_ptrs (ecg_repair.c); ecg_update_masks_ptrs (ecg_update_masks.c,
+ * S x (2k + p) entries and its own three-group strided test) */
 /* a range no cell of a table may share a byte with; `what` names it in the error */
 struct ecg_clear {
 	const void *at;

@@ -1,6 +1,7 @@
 /*
  * ecg_update_masks.c -- aggregation delta parity update with one set of
- * updated cells per stripe (include/ecg.h ecg_update_masks).
+ * updated cells per stripe (include/ecg.h ecg_update_masks,
+ * ecg_update_masks_ptrs).
  *
  * What it replaces: ecg_update takes one cell_idx list for a whole batch, so
  * a batch whose stripes changed different cells is issued as one call per
@@ -14,65 +15,88 @@
  * The tables are the Cauchy parity rows of all k columns, which do not depend
  * on the stripe: they travel in the launch's parameters, so the call needs no
  * per-context table and no synchronous upload.
+ *
+ * ecg_update_masks_ptrs is the same launch for stripes that are not three
+ * strided images: a host table of 2k + p cell addresses per stripe (old, new,
+ * parity), staged through the one path of the cell-table calls
+ * (ecg_internal.h ecg_staged_open / _upload / _close), and the cell-table
+ * kernels of the same file.  A table that is three strided images after all
+ * is handed to ecg_update_masks.  The two calls share the argument check, the
+ * launch helper and its ecg_launch_done.
  */
 #include <stdlib.h>
 #include <string.h>
 
 #include "ecg_internal.h"
 
-int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
-		     const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
-		     void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
-		     const uint32_t *masks, void *result, unsigned flags, void *stream)
+/* The argument checks of both calls in their documented order (fn names the
+ * caller in the message; have_ctx = 0 fails where they report a NULL context).
+ * strided = 1: ecg_update_masks, whose operands are checked before the
+ * context; 0: ecg_update_masks_ptrs, whose table is checked after it (`cells`;
+ * its entries by ecg_staged_open) and which has no packed form. */
+static int um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
+		    const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
+		    int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
+		    unsigned flags)
 {
-	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
-	ecg_mm_params_t *prm;
-	hipStream_t st;
-	uint32_t kid = 0;
-	int rc, e, r, j, bytewise;
-
 	if (k < 1 || k > ECG_KMAX_K || p < 1 || p > ECG_KMAX_R)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: k=%d p=%d outside the limits k <= %d, p <= %d", k, p,
+		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
 				ECG_KMAX_K, ECG_KMAX_R);
 	if (flags & ~(ECG_RM_SPARSE | ECG_UM_PACKED))
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: unknown flags 0x%x", flags);
+		return ecg_fail(-ECG_DER_INVAL, "%s: unknown flags 0x%x", fn, flags);
+	if (!strided && (flags & ECG_UM_PACKED))
+		return ecg_fail(-ECG_DER_INVAL, "%s: ECG_UM_PACKED has no meaning over a cell table (slot j holds "
+				"the address of cell j)", fn);
 	if (masks == NULL || (uintptr_t)masks % 4u)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: masks must be 4-byte aligned device memory");
+		return ecg_fail(-ECG_DER_INVAL, "%s: masks must be 4-byte aligned device memory", fn);
 	if (result == NULL || (uintptr_t)result % 8u)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: result must be 8-byte aligned device memory");
-	if (old_cells == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: NULL old_cells");
-	if (new_cells == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: NULL new_cells");
-	if (parity == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: NULL parity");
-	/* the kernel reads mask words and counts into result while other blocks
-	 * write parity cells */
-	if (S && C && ecg_cells_overlap(masks, 4ull * S, parity, S, parity_stripe_stride, p, parity_cell_stride, C))
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: masks overlaps the parity");
-	if (S && C && ecg_cells_overlap(result, 32, parity, S, parity_stripe_stride, p, parity_cell_stride, C))
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: result overlaps the parity");
-	if (ctx == NULL)
-		return ecg_fail(-ECG_DER_INVAL, "update_masks: NULL context");
-	rc = ecg_ctx_enter(ctx);
-	if (rc)
-		return rc;
-	st = ecg_pick_stream(ctx, stream);
+		return ecg_fail(-ECG_DER_INVAL, "%s: result must be 8-byte aligned device memory", fn);
+	if (strided) {
+		if (old_cells == NULL)
+			return ecg_fail(-ECG_DER_INVAL, "%s: NULL old_cells", fn);
+		if (new_cells == NULL)
+			return ecg_fail(-ECG_DER_INVAL, "%s: NULL new_cells", fn);
+		if (parity == NULL)
+			return ecg_fail(-ECG_DER_INVAL, "%s: NULL parity", fn);
+		/* the kernel reads mask words and counts into result while other
+		 * blocks write parity cells */
+		if (S && C &&
+		    ecg_cells_overlap(masks, 4ull * S, parity, S, parity_stripe_stride, p, parity_cell_stride, C))
+			return ecg_fail(-ECG_DER_INVAL, "%s: masks overlaps the parity", fn);
+		if (S && C && ecg_cells_overlap(result, 32, parity, S, parity_stripe_stride, p, parity_cell_stride, C))
+			return ecg_fail(-ECG_DER_INVAL, "%s: result overlaps the parity", fn);
+	}
+	if (!have_ctx)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	if (!strided && S && C && cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells", fn);
+	return 0;
+}
 
-	/* nothing updated, no invalid mask */
-	rc = ecg_result_reset(result, st, "update_masks memset");
-	if (rc || S == 0 || C == 0)
-		return rc;
+/* The launch of both calls (fn names the call in the trace range and the
+ * messages): over the three strided images, or with cells_dev over the staged
+ * cell table (the strided operands unused). */
+static int um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
+		     const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
+		     int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
+		     void *result, unsigned flags, hipStream_t st)
+{
+	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
+	const int ptrs = cells_dev != NULL;
+	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
+	uint32_t kid = 0;
+	int e, r, j;
 
-	prm = calloc(1, sizeof(*prm));
 	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "update_masks: calloc");
-	prm->src = old_cells;
-	prm->src2 = new_cells;
-	prm->dst = parity;
-	prm->src_stripe_stride = upd_stripe_stride;
-	prm->src2_stripe_stride = upd_stripe_stride;
-	prm->dst_stripe_stride = parity_stripe_stride;
+		return ecg_fail(-ECG_DER_NOMEM, "%s: calloc", fn);
+	if (cells_dev == NULL) {
+		prm->src = old_cells;
+		prm->src2 = new_cells;
+		prm->dst = parity;
+		prm->src_stripe_stride = upd_stripe_stride;
+		prm->src2_stripe_stride = upd_stripe_stride;
+		prm->dst_stripe_stride = parity_stripe_stride;
+	}
 	prm->cell_bytes = C;
 	prm->nstripes = S;
 	prm->k = (uint32_t)k;
@@ -83,18 +107,119 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	ecg_gf_init();
 	ecg_gen_cauchy1(k, p, en);
 	for (r = 0; r < p; r++) {
-		prm->dst_cell_off[r] = (int64_t)r * parity_cell_stride;
+		if (cells_dev == NULL)
+			prm->dst_cell_off[r] = (int64_t)r * parity_cell_stride;
 		for (j = 0; j < k; j++)
 			ecg_build_ptbl(en[(k + r) * k + j], &prm->tbl[r][j]);
 	}
-	bytewise = ctx->cfg.variant == 2 ||
-		   ((uintptr_t)old_cells | (uintptr_t)new_cells | (uintptr_t)parity | (uint64_t)upd_stripe_stride |
-		    (uint64_t)parity_cell_stride | (uint64_t)parity_stripe_stride | C) % 16u;
 
-	ecg_trace_push("ecg:update_masks");
-	e = ecg_k_launch_update_masks(prm, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0, bytewise,
-				      (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kid);
+	ecg_trace_push(ptrs ? "ecg:update_masks_ptrs" : "ecg:update_masks");
+	e = ecg_k_launch_update_masks(prm, cells_dev, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0,
+				      ctx->cfg.variant == 2 || bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg,
+				      (void *)st, &kid);
 	free(prm);
 	/* update_cells / update_bytes stay: the count is known on the device only */
-	return ecg_launch_done(ctx, e, "update_masks kernel launch", 1, ecg_k_update_masks_kernel_name(kid));
+	return ecg_launch_done(ctx, e, ptrs ? "update_masks_ptrs kernel launch" : "update_masks kernel launch", 1,
+			       ecg_k_update_masks_kernel_name(kid));
+}
+
+int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
+		     const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
+		     void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		     const uint32_t *masks, void *result, unsigned flags, void *stream)
+{
+	static const char fn[] = "update_masks";
+	hipStream_t st;
+	int rc;
+
+	rc = um_check(fn, 1, ctx != NULL, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride,
+		      parity_stripe_stride, NULL, masks, result, flags);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+
+	/* nothing updated, no invalid mask */
+	rc = ecg_result_reset(result, st, "update_masks memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
+	return um_launch(ctx, fn, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity, parity_cell_stride,
+			 parity_stripe_stride, NULL,
+			 ((uintptr_t)old_cells | (uintptr_t)new_cells | (uintptr_t)parity | (uint64_t)upd_stripe_stride |
+			  (uint64_t)parity_cell_stride | (uint64_t)parity_stripe_stride | C) % 16u != 0,
+			 masks, result, flags, st);
+}
+
+/* Is the staged table tab[S][2k + p] three strided groups -- old cell (s, j)
+ * at o0 + s*us + j*C, new cell (s, j) at n0 + s*us + j*C with the same us,
+ * parity (s, r) at p0 + s*ps + r*pc?  One stripe is, when its cells are spaced
+ * so.  The strides are differences of addresses and may be negative. */
+static int um_three_groups(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *us, int64_t *pc,
+			   int64_t *ps)
+{
+	const uint32_t n = (uint32_t)(2 * k + p);
+	const uint64_t o0 = tab[0], n0 = tab[k], p0 = tab[2 * k];
+	const uint64_t u = S > 1 ? tab[n] - o0 : (uint64_t)k * C;
+	const uint64_t c = p > 1 ? tab[2 * k + 1] - p0 : C;
+	const uint64_t q = S > 1 ? tab[n + 2 * k] - p0 : C;
+	int aff = 1;
+
+	for (uint64_t s = 0; s < S; s++) {
+		const uint64_t *row = tab + s * n;
+
+		for (int j = 0; j < k; j++) {
+			aff &= row[j] == o0 + s * u + (uint64_t)j * C;
+			aff &= row[k + j] == n0 + s * u + (uint64_t)j * C;
+		}
+		for (int r = 0; r < p; r++)
+			aff &= row[2 * k + r] == p0 + s * q + (uint64_t)r * c;
+	}
+	*us = (int64_t)u;
+	*pc = (int64_t)c;
+	*ps = (int64_t)q;
+	return aff;
+}
+
+int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+			  const uint32_t *masks, void *result, unsigned flags, void *stream)
+{
+	static const char fn[] = "update_masks_ptrs";
+	/* the kernel reads mask words and counts into result while other blocks
+	 * write parity cells */
+	const struct ecg_clear clear[2] = {{masks, 4ull * S, "masks"}, {result, 32, "result"}};
+	struct ecg_staged t;
+	int64_t us, pc, ps;
+	hipStream_t st;
+	int rc;
+
+	rc = um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing updated, no invalid mask */
+		return ecg_result_reset(result, st, "update_masks_ptrs memset");
+
+	rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(2 * k + p), C, clear, 2, &t);
+	if (rc)
+		return rc;
+	/* ecg_update_masks's own layout (and masks and result clear of the whole
+	 * parity span, gaps included, as it demands): its launch, with no table
+	 * and no dependent address loads */
+	if (um_three_groups(t.sc->pin, k, p, C, S, &us, &pc, &ps) &&
+	    !ecg_cells_overlap(masks, 4ull * S, cells[2 * k], S, ps, p, pc, C) &&
+	    !ecg_cells_overlap(result, 32, cells[2 * k], S, ps, p, pc, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_update_masks(ctx, k, p, C, S, cells[0], cells[k], us, cells[2 * k], pc, ps, masks, result,
+					flags, stream);
+	}
+	rc = ecg_staged_upload(&t, result, st, "update_masks_ptrs memset", "update_masks_ptrs cell table");
+	if (rc == 0)
+		rc = um_launch(ctx, fn, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks,
+			       result, flags, st);
+	return ecg_staged_close(ctx, &t, st, rc);
 }

@@ -1,7 +1,7 @@
 // ecg_update_masks_kernels.hip -- aggregation delta parity update with one
-// set of updated cells per stripe (ecg_update_masks): agg_update_parity's
-// bit_map (ref:src/object/srv_ec_aggregate.c:1006-1105) as a mask word per
-// stripe in device memory, a whole batch in one launch.
+// set of updated cells per stripe (ecg_update_masks, ecg_update_masks_ptrs):
+// agg_update_parity's bit_map (ref:src/object/srv_ec_aggregate.c:1006-1105) as
+// a mask word per stripe in device memory, a whole batch in one launch.
 //
 //     parity[s][r] ^= XOR_{j in masks[s]} g[k+r][j] * (old[s][j] ^ new[s][j])
 //
@@ -17,8 +17,17 @@
 // delta into the rows (ecg_mm_dev.h upd_fold), and stores each parity row
 // once: (2 n + 2 p) C bytes per stripe of n changed cells.
 //
+// Two layouts, one body each for the lane and the byte kernels (um_lanes,
+// um_bytes): three strided images (old, new, parity), or a table of cell
+// addresses, row s = cells + s * (2k + p): k old cells, k new cells, p parity
+// cells, for callers whose stripes are separate buffers (aggregation holds one
+// stripe's buffers at a time).  The bodies ask an addressing struct
+// (um_strided, um_table) where a stripe's cells are and share everything else;
+// the __global__ entry points only choose it.
+//
 // A column index is the position of a set bit of a mask that has no bit at or
-// above k, so every table and cell address is bounded whatever the word holds:
+// above k, so every table and cell address is bounded whatever the word holds
+// (and read inside the stripe's row of a cell table):
 // all 2^32 mask values are safe.  A stripe's parity cells are written by the
 // one block row that owns the stripe, each byte by one lane.
 //
@@ -61,20 +70,82 @@ __device__ __forceinline__ uint64_t um_cell(uint32_t packed, uint32_t i, uint32_
 	return (uint64_t)(packed ? i : j) * C;
 }
 
-} // namespace
+// Where a stripe's cells are -- all the strided and the cell-table kernels
+// differ in.  A body positions the struct on a stripe (at), binds parity row r
+// once per stripe (bind), asks per column for the row's address (par) and,
+// per set bit j of the mask (the i-th in ascending order), for the addresses
+// of the old and the new cell at the column's offset (pair).
 
-// R = p parity rows (1..3 specialised; 0 = runtime-shaped, 4..8 rows).
-// 16-byte lanes only: every operand, stride and C a 16-byte multiple (the
-// launcher sends everything else to the byte kernel), so a partial last
-// column is a lane mask.
-template <int R>
-__global__ void __launch_bounds__(BLOCK)
-ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks, unsigned long long *result,
-			uint32_t grp, uint32_t packed)
+// Three strided images: every address is arithmetic on the stripe's three
+// bases, done per column, so nothing is bound.
+// The launch's bases and strides are held by value (read once, in front of
+// the row loop, where the kernel written without the struct read them).
+struct um_strided {
+	const uint8_t *src, *src2;
+	uint8_t *dst;
+	int64_t ss, s2s, ds;
+	const int64_t *doff;
+	uint64_t C;
+	uint32_t packed;
+	const uint8_t *ob, *nb;
+	uint8_t *pb;
+
+	__device__ um_strided(const ecg_mm_params_t &P, uint32_t packed_)
+		: src(P.src), src2(P.src2), dst(P.dst), ss(P.src_stripe_stride), s2s(P.src2_stripe_stride),
+		  ds(P.dst_stripe_stride), doff(P.dst_cell_off), C(P.cell_bytes), packed(packed_) {}
+	__device__ void at(uint32_t s)
+	{
+		ob = src + (int64_t)s * ss;
+		nb = src2 + (int64_t)s * s2s;
+		pb = dst + (int64_t)s * ds;
+	}
+	__device__ void bind(int) {}
+	__device__ uint8_t *par(int r) const { return pb + doff[r]; }
+	__device__ void pair(uint32_t i, uint32_t j, uint64_t off, const uint8_t **o, const uint8_t **n) const
+	{
+		const uint64_t c = um_cell(packed, i, j, C) + off;
+
+		*o = ob + c;
+		*n = nb + c;
+	}
+};
+
+// The stripe's row pt of a cell table: old cell j = pt[j], new cell j =
+// pt[k + j], parity row r = pt[2k + r].  Wave-uniform: the stripe index and
+// the mask word come from a readlane, so these are scalar loads of a read-only
+// table.  The RM parity addresses are bound once per stripe, before the column
+// loop; the two addresses of a named cell are loaded per set bit inside it,
+// which keeps the registers flat (up to 16 named cells would be 64 SGPRs bound)
+// and costs the dense grid nothing: there a block takes one column of a stripe.
+template <int RM>
+struct um_table {
+	const uint64_t *__restrict__ cells;
+	uint32_t k, n;	// n = 2k + p
+	const uint64_t *__restrict__ pt;
+	uint64_t slot[RM];	// those bound, the rest left unset
+
+	__device__ um_table(const uint64_t *cells_, uint32_t k_, uint32_t p_) : cells(cells_), k(k_), n(2u * k_ + p_) {}
+	__device__ void at(uint32_t s) { pt = cells + (uint64_t)s * n; }
+	__device__ void bind(int r) { slot[r] = pt[2u * k + (uint32_t)r]; }
+	__device__ uint8_t *par(int r) const { return reinterpret_cast<uint8_t *>(slot[r]); }
+	__device__ void pair(uint32_t, uint32_t j, uint64_t off, const uint8_t **o, const uint8_t **n_) const
+	{
+		*o = reinterpret_cast<const uint8_t *>(pt[j]) + off;
+		*n_ = reinterpret_cast<const uint8_t *>(pt[k + j]) + off;
+	}
+};
+
+// The lane kernels' body.  R = p parity rows (1..3 specialised; 0 =
+// runtime-shaped, 4..8 rows).  16-byte lanes only: every cell address (strided:
+// every operand and stride) and C a 16-byte multiple (the launcher sends
+// everything else to the byte kernel), so a partial last column is a lane
+// mask.  s_tbl: the block's ECG_TBL_WORDS(ECG_KMAX_K, RM) staged table words.
+template <int R, class Addr>
+__device__ __forceinline__ void um_lanes(const ecg_mm_params_t &P, u32x4 *s_tbl, const uint32_t *__restrict__ masks,
+					 unsigned long long *result, uint32_t grp, Addr A)
 {
 	constexpr int RM = R ? R : ECG_KMAX_R;
 	using TB = mm_tbl<RM>;
-	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, RM)];
 	const int k = (int)P.k;
 	const int rows = R ? R : (int)P.rows;
 	const uint64_t C = P.cell_bytes;
@@ -91,9 +162,12 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 
 		while (todo) {
 			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
-			const uint8_t *ob = P.src + (int64_t)s * P.src_stripe_stride;
-			const uint8_t *nb = P.src2 + (int64_t)s * P.src2_stripe_stride;
-			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
+
+			A.at(s);
+#pragma unroll
+			for (int r = 0; r < RM; r++)
+				if (r < rows)
+					A.bind(r);
 
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t off = (uint64_t)ch * CHUNK_BYTES + lo;
@@ -105,11 +179,13 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 #pragma unroll
 				for (int r = 0; r < RM; r++)
 					if (r < rows)
-						acc[r] = ld_g<16>(pb + P.dst_cell_off[r] + off);
+						acc[r] = ld_g<16>(A.par(r) + off);
 				for (uint32_t mm = m, i = 0; mm; i += 2) {
 					const uint32_t j0 = (uint32_t)__builtin_ctz(mm);
-					const uint64_t c0 = um_cell(packed, i, j0, C) + off;
-					const u32x4 x0 = ld_g<16>(ob + c0) ^ ld_g<16>(nb + c0);
+					const uint8_t *o0, *n0, *o1, *n1;
+
+					A.pair(i, j0, off, &o0, &n0);
+					const u32x4 x0 = ld_g<16>(o0) ^ ld_g<16>(n0);
 					u32x4 x1 = (u32x4){0u, 0u, 0u, 0u};
 					uint32_t j1 = 0;
 
@@ -118,8 +194,8 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 					if (two) {
 						j1 = (uint32_t)__builtin_ctz(mm);
 						mm &= mm - 1u;
-						const uint64_t c1 = um_cell(packed, i + 1u, j1, C) + off;
-						x1 = ld_g<16>(ob + c1) ^ ld_g<16>(nb + c1);
+						A.pair(i + 1u, j1, off, &o1, &n1);
+						x1 = ld_g<16>(o1) ^ ld_g<16>(n1);
 					}
 					// (the unsigned bit index times PER_J, not TB::cell's int:
 					// that one folds into another scalar sequence)
@@ -130,18 +206,19 @@ ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ ma
 #pragma unroll
 				for (int r = 0; r < RM; r++)
 					if (r < rows)
-						st_g<16>(pb + P.dst_cell_off[r] + off, acc[r]);
+						st_g<16>(A.par(r) + off, acc[r]);
 			}
 		}
 	}
 }
 
-// Any alignment, any length, any p <= 8: a block takes 4 KiB columns of one
-// stripe at a time, a lane the bytes t, t + 256, ... of a column.  Same scan
-// and counters as the lane kernel; the tables are read where they lie.
-__global__ void __launch_bounds__(BLOCK)
-ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks,
-			     unsigned long long *result, uint32_t grp, uint32_t packed)
+// The byte kernels' body.  Any alignment, any length, any p <= 8: a block
+// takes 4 KiB columns of one stripe at a time, a lane the bytes t, t + 256, ...
+// of a column.  Same scan and counters as the lane body; the tables are read
+// where they lie.
+template <class Addr>
+__device__ __forceinline__ void um_bytes(const ecg_mm_params_t &P, const uint32_t *__restrict__ masks,
+					 unsigned long long *result, uint32_t grp, Addr A)
 {
 	const uint64_t C = P.cell_bytes;
 	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
@@ -155,9 +232,12 @@ ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict
 
 		while (todo) {
 			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
-			const uint8_t *ob = P.src + (int64_t)s * P.src_stripe_stride;
-			const uint8_t *nb = P.src2 + (int64_t)s * P.src2_stripe_stride;
-			uint8_t *pb = P.dst + (int64_t)s * P.dst_stripe_stride;
+
+			A.at(s);
+#pragma unroll
+			for (int r = 0; r < ECG_KMAX_R; r++)
+				if (r < rows)
+					A.bind(r);
 
 			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
 				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
@@ -169,8 +249,10 @@ ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict
 						o[r] = 0;
 					for (uint32_t mm = m, i = 0; mm; mm &= mm - 1u, i++) {
 						const uint32_t j = (uint32_t)__builtin_ctz(mm);
-						const uint64_t c = um_cell(packed, i, j, C) + b;
-						const uint32_t v = (uint32_t)ob[c] ^ (uint32_t)nb[c];
+						const uint8_t *oc, *nc;
+
+						A.pair(i, j, b, &oc, &nc);
+						const uint32_t v = (uint32_t)*oc ^ (uint32_t)*nc;
 
 #pragma unroll
 						for (int r = 0; r < ECG_KMAX_R; r++)
@@ -180,79 +262,137 @@ ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict
 #pragma unroll
 					for (int r = 0; r < ECG_KMAX_R; r++)
 						if (r < rows)
-							pb[P.dst_cell_off[r] + (int64_t)b] ^= (uint8_t)o[r];
+							A.par(r)[b] ^= (uint8_t)o[r];
 				}
 			}
 		}
 	}
 }
 
+} // namespace
+
+// The entry points: the strided images P.src / P.src2 / P.dst
+// (ecg_update_masks), or the table `cells` (ecg_update_masks_ptrs).
+template <int R>
+__global__ void __launch_bounds__(BLOCK)
+ecg_update_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks, unsigned long long *result,
+			uint32_t grp, uint32_t packed)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, R ? R : ECG_KMAX_R)];
+
+	um_lanes<R>(P, s_tbl, masks, result, grp, um_strided(P, packed));
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_update_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks,
+			     unsigned long long *result, uint32_t grp, uint32_t packed)
+{
+	um_bytes(P, masks, result, grp, um_strided(P, packed));
+}
+
+template <int R>
+__global__ void __launch_bounds__(BLOCK)
+ecg_update_masks_ptr_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells,
+			    const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, R ? R : ECG_KMAX_R)];
+
+	um_lanes<R>(P, s_tbl, masks, result, grp, um_table<R ? R : ECG_KMAX_R>(cells, P.k, R ? R : P.rows));
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_update_masks_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells,
+				 const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp)
+{
+	um_bytes(P, masks, result, grp, um_table<ECG_KMAX_R>(cells, P.k, P.rows));
+}
+
 // ---------------------------------------------------------------------------
-// Dispatch
+// Dispatch: one table for both layouts.  The lane instantiations, then the
+// byte kernels; an entry's index is its kernel id above ECG_KID_UPDATE_MASKS
+// (strided) or ECG_KID_UPDATE_MASKS_PTRS (cell table).
 // ---------------------------------------------------------------------------
 typedef void (*um_fn_t)(const ecg_mm_params_t, const uint32_t *, unsigned long long *, uint32_t, uint32_t);
+typedef void (*ump_fn_t)(const ecg_mm_params_t, const uint64_t *, const uint32_t *, unsigned long long *, uint32_t);
 
 struct umentry {
 	int r;
 	um_fn_t fn;
-	const char *name;
+	ump_fn_t pfn;
+	const char *name, *pname;
 };
 
-#define UME(R_) {R_, ecg_update_masks_kernel<R_>, "ecg_update_masks_kernel<" #R_ ">"}
+#define UME(R_)                                                                                                        \
+	{R_, ecg_update_masks_kernel<R_>, ecg_update_masks_ptr_kernel<R_>, "ecg_update_masks_kernel<" #R_ ">",        \
+	 "ecg_update_masks_ptr_kernel<" #R_ ">"}
 
 // the DAOS classes' p = 1..3 specialised, 4..8 parity rows runtime-shaped
-static const umentry g_um[] = {UME(1), UME(2), UME(3), UME(0)};
+static const umentry g_um[] = {UME(1), UME(2), UME(3), UME(0),
+			       {-1, ecg_update_masks_byte_kernel, ecg_update_masks_ptr_byte_kernel,
+				"ecg_update_masks_byte_kernel", "ecg_update_masks_ptr_byte_kernel"}};
 #define N_UM ((uint32_t)(sizeof(g_um) / sizeof(g_um[0])))
-#define KID_UM_BYTE (ECG_KID_UPDATE_MASKS + N_UM)
+#define UM_BYTE (N_UM - 1)
+static_assert(ECG_KID_UPDATE_MASKS + N_UM <= ECG_KID_UPDATE_MASKS_PTRS &&
+		      ECG_KID_UPDATE_MASKS_PTRS + N_UM <= ECG_KID_COPY_SEGS,
+	      "update_masks ids: 890 .. 894 strided, 895 .. 899 cell table");
 
 extern "C" const char *ecg_k_update_masks_kernel_name(uint32_t id)
 {
 	if (id >= ECG_KID_UPDATE_MASKS && id < ECG_KID_UPDATE_MASKS + N_UM)
 		return g_um[id - ECG_KID_UPDATE_MASKS].name;
-	if (id == KID_UM_BYTE)
-		return "ecg_update_masks_byte_kernel";
+	if (id >= ECG_KID_UPDATE_MASKS_PTRS && id < ECG_KID_UPDATE_MASKS_PTRS + N_UM)
+		return g_um[id - ECG_KID_UPDATE_MASKS_PTRS].pname;
 	return "?";
 }
 
-extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint32_t *masks, uint64_t *result,
-					 int packed, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
-					 void *stream, uint32_t *kernel_id)
+extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+					 uint64_t *result, int packed, int bytewise, int sparse,
+					 const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
 {
 	hipStream_t st = (hipStream_t)stream;
-	uint32_t gx, gy;
+	uint32_t gx, gy, id = UM_BYTE;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0)
 		return (int)hipSuccess;
 	if (p->k == 0 || p->k > ECG_KMAX_K || p->rows == 0 || p->rows > ECG_KMAX_R || masks == nullptr ||
-	    result == nullptr || p->src == nullptr || p->src2 == nullptr || p->dst == nullptr ||
-	    p->src_stripe_stride != p->src2_stripe_stride)
+	    result == nullptr)
+		return (int)hipErrorInvalidValue;
+	if (cells_dev == nullptr && (p->src == nullptr || p->src2 == nullptr || p->dst == nullptr ||
+				     p->src_stripe_stride != p->src2_stripe_stride))
+		return (int)hipErrorInvalidValue;
+	if (cells_dev != nullptr && packed)	// a table has an address in slot j
 		return (int)hipErrorInvalidValue;
 	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
 
 	rows_grid(p, grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, &gx, &gy);
 
-	if (bytewise) {
-		hipLaunchKernelGGL(ecg_update_masks_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks,
-				   (unsigned long long *)result, grp, (uint32_t)(packed != 0));
-		if (kernel_id)
-			*kernel_id = KID_UM_BYTE;
-		return (int)hipGetLastError();
-	}
-	// the lane kernel reads and writes dwordx4 at the cells' own addresses
-	uint64_t al = (uint64_t)(uintptr_t)p->src | (uint64_t)(uintptr_t)p->src2 | (uint64_t)(uintptr_t)p->dst |
-		      (uint64_t)p->src_stripe_stride | (uint64_t)p->dst_stripe_stride | p->cell_bytes;
-	for (uint32_t r = 0; r < p->rows; r++)
-		al |= (uint64_t)p->dst_cell_off[r];
-	if ((al & 15u) != 0)
-		return (int)hipErrorInvalidValue;
+	if (!bytewise) {
+		// the lane kernel reads and writes dwordx4 at the cells' own addresses;
+		// those of a cell table the host has found 16-byte aligned (the table
+		// is not read here)
+		uint64_t al = p->cell_bytes;
 
-	uint32_t id = N_UM;
-	for (uint32_t i = 0; i < N_UM && id == N_UM; i++)
-		if (g_um[i].r == (int)p->rows || g_um[i].r == 0)
-			id = i;
-	hipLaunchKernelGGL(g_um[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks, (unsigned long long *)result,
-			   grp, (uint32_t)(packed != 0));
+		if (cells_dev == nullptr) {
+			al |= (uint64_t)(uintptr_t)p->src | (uint64_t)(uintptr_t)p->src2 | (uint64_t)(uintptr_t)p->dst |
+			      (uint64_t)p->src_stripe_stride | (uint64_t)p->dst_stripe_stride;
+			for (uint32_t r = 0; r < p->rows; r++)
+				al |= (uint64_t)p->dst_cell_off[r];
+		}
+		if ((al & 15u) != 0)
+			return (int)hipErrorInvalidValue;
+		for (id = 0; id < UM_BYTE; id++)
+			if (g_um[id].r == (int)p->rows || g_um[id].r == 0)
+				break;
+		if (id == UM_BYTE)
+			return (int)hipErrorInvalidValue;
+	}
+	if (cells_dev == nullptr)
+		hipLaunchKernelGGL(g_um[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks, (unsigned long long *)result,
+				   grp, (uint32_t)(packed != 0));
+	else
+		hipLaunchKernelGGL(g_um[id].pfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, cells_dev, masks,
+				   (unsigned long long *)result, grp);
 	if (kernel_id)
-		*kernel_id = ECG_KID_UPDATE_MASKS + id;
+		*kernel_id = (cells_dev ? ECG_KID_UPDATE_MASKS_PTRS : ECG_KID_UPDATE_MASKS) + id;
 	return (int)hipGetLastError();
 }

@@ -61,6 +61,8 @@ _SIGS = [
                              vp, C.c_int64, C.c_int64, vp]),
     ("ecg_update_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, C.c_int64, vp, C.c_int64,
                                    C.c_int64, vp, vp, C.c_uint, vp]),
+    ("ecg_update_masks_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
+                                        C.c_uint, vp]),
     ("ecg_verify",C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_verify_cell", C.c_int, [C.c_uint32, C.c_int, C.c_int]),
@@ -646,6 +648,16 @@ class Context:
         _chk(lib().ecg_update_masks(self.h, k, p, cell_bytes, nstripes, old, new, upd_stripe_stride, parity,
                                     parity_cell_stride, parity_stripe_stride, masks, result, flags, stream),
              "update_masks")
+
+    def update_masks_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None,
+                          masks: int, result: int, flags: int = 0, stream=None):
+        """ecg_update_masks_ptrs: update_masks() over a table of cell addresses -- row s of
+        cells is [s*(2k+p) + j]: old data cell j, [.. + k + j]: new data cell j, [.. + 2k + r]:
+        parity cell r (or a ctypes array of c_void_p, passed as it is; the library has copied it
+        when the call returns).  masks and result as update_masks()'s; flags: RM_SPARSE (tuning
+        only), UM_PACKED is refused."""
+        _chk(lib().ecg_update_masks_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks, result,
+                                         flags, stream), "update_masks_ptrs")
 
     def verify(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
                parity: int, parity_cell_stride: int, parity_stripe_stride: int, status: int, result: int,

@@ -226,6 +226,63 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t
 		     const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
 		     void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
 		     const uint32_t *masks, void *result, unsigned flags, void *stream);
+/* ecg_update_masks over a TABLE OF CELL ADDRESSES, for callers whose stripes
+ * are not three strided images: agg_update_parity works on one stripe's
+ * buffers at a time (ref:src/object/srv_ec_aggregate.c:1006-1105), so a batch
+ * of stripes is a set of separate allocations.  cells: HOST array of nstripes
+ * * (2k+p) device addresses; row s is
+ *   cells[s*(2k+p) + j],      j < k   old data cell j of stripe s
+ *   cells[s*(2k+p) + k + j],  j < k   new data cell j
+ *   cells[s*(2k+p) + 2k + r], r < p   parity cell r
+ * every cell cell_bytes long, at any address.  The table is staged internally
+ * as in the other _ptrs calls, so the caller may overwrite or free it as soon
+ * as the call returns.  Every entry is checked, named by a mask or not (the
+ * host never sees the masks).  With the masks on the device (ecg_csum.h:
+ * ecg_csum_cells_ptrs over this table -> ecg_memset(masks, 0) -> ecg_csum_mask
+ * (got = the old cells' slots, want = the new cells' slots) ->
+ * ecg_update_masks_ptrs) the host need not know which cells changed.
+ * masks, result, ECG_RM_SPARSE and what happens to a stripe are
+ * ecg_update_masks's, word for word: m == 0 leaves the stripe untouched and
+ * uncounted; a bit at or above k leaves it untouched and counts it in
+ * result[3] and result[1]; any other m leaves parity_r ^= XOR_{j in m}
+ * g[k+r][j] * (old_j ^ new_j), the bytes ecg_update_masks leaves on a
+ * contiguous copy of that stripe, and nothing else is written.  All 2^32 mask
+ * values are safe: an index into a table row is always j, k + j or 2k + r with
+ * j a set bit of a word that has no bit at or above k.  result = {0,
+ * UINT64_MAX, 0, 0} also for nstripes == 0 or cell_bytes == 0; INVALID MASKS
+ * ARE REPORTED THROUGH result ONLY.  Limits k <= 16, p <= 8.
+ * flags: ECG_RM_SPARSE, the same tuning hint and the same two grids.
+ * ECG_UM_PACKED is refused: a table makes packing pointless, the caller puts
+ * an address in slot j.
+ * -ECG_DER_INVAL, the message prefixed "update_masks_ptrs:", checked in this
+ * order: the k / p limits; an unknown flag, or ECG_UM_PACKED; masks NULL or
+ * not 4-byte aligned; result NULL or not 8-byte aligned (both also for
+ * nstripes == 0); a NULL context; cells NULL (nstripes and cell_bytes != 0); a
+ * NULL entry (the message names its index); masks (4 * nstripes bytes) or
+ * result (32 bytes) sharing a byte with any cell ("overlaps", with the cell's
+ * index).
+ * NOT CHECKED, THE CALLER'S CONTRACT: NO PARITY CELL OF THE TABLE MAY OVERLAP
+ * ANY OTHER CELL THE LAUNCH READS OR WRITES -- THE PARITY CELLS OF ANOTHER ROW
+ * INCLUDED: TWO STRIPES NAMING ONE PARITY CELL RACE -- AND EVERY CELL IS MEMORY
+ * OF THE CONTEXT'S DEVICE.  Read-only duplicates are allowed: an old entry may
+ * equal a new entry (that cell then contributes nothing), and old or new cells
+ * may be shared between rows.
+ * A table that is three strided groups -- old cell (s, j) at o0 + s*us + j*
+ * cell_bytes, new cell (s, j) at n0 + s*us + j*cell_bytes with the same us,
+ * parity (s, r) at p0 + s*ps + r*pc; one stripe whose cells are spaced so
+ * always is -- and whose arguments pass ecg_update_masks's own checks (masks
+ * and result clear of the whole parity span, gaps included) IS the call
+ * ecg_update_masks(old = o0, new = n0, us, parity = p0, pc, ps): no table is
+ * uploaded and ecg_last_kernel names that strided kernel.  Any other table
+ * runs ecg_update_masks_ptr_kernel<R> (16-byte lanes) when every entry and
+ * cell_bytes are multiples of 16, and ecg_update_masks_ptr_byte_kernel for the
+ * WHOLE launch when one is not, or with ecg_set_launch variant 2;
+ * ecg_set_launch's grid_x / grid_y override either grid.  Asynchronous on
+ * `stream`.  Telemetry as ecg_update_masks: `launches` counts the launch,
+ * update_cells / update_bytes are not advanced. */
+int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			  void *const *cells, const uint32_t *masks, void *result,
+			  unsigned flags, void *stream);
 
 /* Parity consistency check: does the stored parity of every stripe still
  * match its stored data -- what the EC branch of the object verify path

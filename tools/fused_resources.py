@@ -33,8 +33,8 @@ report`).  Needs no GPU.
       uses scratch; every kernel of BASE must show identical figures in NEW
       (exit 1 on any difference)
   python tools/fused_resources.py --update-masks UM.txt [NEW.txt BASE.txt]...
-      the ecg_update_masks kernels (remarks of
-      ecg_update_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
+      the ecg_update_masks kernels, strided and cell-table (ptr) alike
+      (remarks of ecg_update_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
       exit 1 if one uses scratch.  NEW BASE pairs as for --repair (upd_fold
       moved into ecg_mm_dev.h)
   python tools/fused_resources.py --kept NEW.txt BASE.txt [NEW.txt BASE.txt]...
@@ -127,7 +127,7 @@ def verify_table(verify_txt, product_txt=None):
 
 REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
-UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
+UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 ANY = re.compile(r"(\S+)()()")
 
 
