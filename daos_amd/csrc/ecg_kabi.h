@@ -109,7 +109,6 @@ typedef struct ecg_launch_cfg {
  * with NB = W/8, T = uint32_t (W <= 32) or uint64_t (W = 64).
  */
 #define ECG_CSUM_STRIDE 1024	/* bytes a wave consumes per step (64 lanes x 16 B) */
-#define ECG_KID_CSUM 1000	/* kernel ids of the checksum kernels start here */
 
 #define ECG_MMCS_STRIDE 4096	/* fused kernels: 256 threads x 16 B per step */
 #define ECG_CSUM_NP2 48
@@ -272,8 +271,6 @@ typedef struct ecg_copy_seg {
 	uint64_t tile0;
 } ecg_copy_seg_t;
 
-#define ECG_KID_COPY_SEGS 900
-
 /*
  * Parity consistency check (kernels/ecg_verify_kernels.hip, ecg_verify): a
  * launch computes the syndrome stored_parity[r] ^ XOR_j coef[r][j] * data[j]
@@ -309,10 +306,14 @@ static inline ECG_KABI_HD int ecg_verify_classify(uint32_t status, int k, int p)
 	return -2;
 }
 
-#define ECG_KID_VERIFY 800u	/* verify kernel ids start here (below ECG_KID_COPY_SEGS) */
-#define ECG_KID_VERIFY_PTRS 836u	/* ids of the cell-table verify kernels (836 .. 849: the 13 lane kernels and
-					 * the byte kernel, above the cell-table recover_masks kernels' 820 .. 835,
-					 * below ECG_KID_REPAIR) */
+/*
+ * Every ecg_k_launch_* below that ends in `const char **kernel` reports the
+ * kernel it launched: on a launch it stores that kernel's name there, a string
+ * with static storage (a literal, or its dispatch table entry's name / pname).
+ * kernel may be NULL.  A call that launches nothing -- the early success for an
+ * empty batch, and every error return before the launch -- leaves *kernel as
+ * it is.
+ */
 
 #ifdef __cplusplus
 extern "C" {
@@ -329,16 +330,15 @@ extern "C" {
  * (device memory, read only for the launch); p->src / dst, the strides and the
  * cell offsets are then unused, and bytewise is the host's lane choice, 0 only
  * when EVERY table entry and cell_bytes are multiples of 16: the launcher does
- * not read the table.  ecg_k_verify_kernel_name serves the ids of both
- * layouts. */
+ * not read the table.  *kernel: ecg_verify_kernel<k,p> / ecg_verify_byte_kernel,
+ * or their ecg_verify_ptr_* counterparts over a table. */
 int ecg_k_launch_verify(const ecg_mm_params_t *p, const uint64_t *cells_dev, uint32_t *status, int bytewise,
-			const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
+			const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* result[0] += bad stripes, result[1] = min(result[1], lowest bad stripe),
  * result[2] += stripes ecg_verify_classify attributes to one cell, result[3]
  * += bad stripes it does not; the host presets {0, UINT64_MAX, 0, 0}. */
 int ecg_k_launch_verify_summary(const uint32_t *status, uint32_t nstripes, int k, int p,
 				uint64_t *result, void *stream);
-const char *ecg_k_verify_kernel_name(uint32_t kernel_id);
 /* Repair pass of ecg_repair (kernels/ecg_repair_kernels.hip): p as for
  * ecg_k_launch_verify (src the data cells, dst the parity rows, rows = p;
  * p->tbl unused), status[nstripes] the words a verify of the same operands
@@ -361,16 +361,12 @@ const char *ecg_k_verify_kernel_name(uint32_t kernel_id);
  * strides and the cell offsets unused: the sources of c >= k are the entries 0
  * .. k-1, those of c < k the same with entry k in slot c, the destination
  * entry c.  bytewise = 0 then only when EVERY table entry and cell_bytes are
- * multiples of 16 (the host's check).  ecg_k_repair_kernel_name serves the ids
- * of both layouts. */
+ * multiples of 16 (the host's check).  *kernel: ecg_repair_kernel<k> /
+ * ecg_repair_byte_kernel, or their ecg_repair_ptr_* counterparts over a table. */
 #define ECG_REPAIR_GRID_X 64u
-#define ECG_KID_REPAIR 850u	/* ids of the strided repair kernels start here (850 .. 855) */
-#define ECG_KID_REPAIR_PTRS 856u	/* ids of the cell-table repair kernels (856 .. 861: the 5 lane kernels and
-					 * the byte kernel, below ECG_KID_RECOVER_MASKS) */
 int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint64_t *cells_dev,
 			const uint32_t *status, uint64_t *result, int bytewise, const ecg_launch_cfg_t *cfg,
-			void *stream, uint32_t *kernel_id);
-const char *ecg_k_repair_kernel_name(uint32_t kernel_id);
+			void *stream, const char **kernel);
 #ifdef __cplusplus
 }
 #endif
@@ -557,16 +553,13 @@ extern "C" {
  * multiples of 16; cell table: EVERY table entry 16-byte aligned (the host's
  * check: the launcher does not read the table) and cell_bytes % 16 == 0
  * (hipErrorInvalidValue otherwise); 1: the byte-granular kernel.
- * ecg_k_recover_masks_kernel_name serves the ids of both layouts. */
+ * *kernel: ecg_recover_masks_kernel<k, p> / ecg_recover_masks_byte_kernel, or
+ * their ecg_recover_masks_ptr_* counterparts over a table. */
 #define ECG_RM_DENSE_GRP 1u
 #define ECG_RM_DENSE_GRID_X 256u
-#define ECG_KID_RECOVER_MASKS 870u	/* ids of the strided recover_masks kernels start here (below ECG_KID_COPY_SEGS) */
-#define ECG_KID_RECOVER_MASKS_PTRS 820u	/* ids of the cell-table recover_masks kernels (820 .. 835: above the
-					 * verify kernels' 800 .. 814, below ECG_KID_REPAIR) */
 int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint64_t *cells_dev,
 			       const uint32_t *masks, uint64_t *result, int bytewise, int sparse,
-			       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
-const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
+			       const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* ecg_update_masks: p->src / p->src2 = the old / new cells (stripe s at +
  * s * src_stripe_stride, the same stride for both; cell j at + j * cell_bytes,
  * or with `packed` the cell of the mask's i-th set bit at + i * cell_bytes),
@@ -591,27 +584,24 @@ const char *ecg_k_recover_masks_kernel_name(uint32_t kernel_id);
  * and `packed` must be 0 (hipErrorInvalidValue).  bytewise = 0 over a table:
  * EVERY table entry 16-byte aligned (the host's check: the launcher does not
  * read the table) and cell_bytes % 16 == 0.
- * ecg_k_update_masks_kernel_name serves the ids of both layouts. */
-#define ECG_KID_UPDATE_MASKS 890u	/* ids of the strided update_masks kernels start here (890 .. 894) */
-#define ECG_KID_UPDATE_MASKS_PTRS 895u	/* ids of the cell-table update_masks kernels (895 .. 899: the 4 lane
-					 * kernels and the byte kernel, below ECG_KID_COPY_SEGS) */
+ * *kernel: ecg_update_masks_kernel<p> / ecg_update_masks_byte_kernel, or their
+ * ecg_update_masks_ptr_* counterparts over a table. */
 int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
 			      uint64_t *result, int packed, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
-			      void *stream, uint32_t *kernel_id);
-const char *ecg_k_update_masks_kernel_name(uint32_t kernel_id);
+			      void *stream, const char **kernel);
 /* ecg_csum_mask (kernels/ecg_csum_kernels.hip): masks[s] |= 1u << (first_cell
  * + i) when any of the nch checksums of len (2, 4 or 8) bytes at index
  * s*stripe_stride + i*cell_stride + c differs between got and want. */
 int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
 			   uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride, uint32_t first_cell,
-			   uint32_t len, uint32_t *masks, void *stream, uint32_t *kernel_id);
+			   uint32_t len, uint32_t *masks, void *stream, const char **kernel);
 /* ecg_csum_masked and, with p->cells_dev, ecg_csum_masked_ptrs (kernels/
  * ecg_csum_kernels.hip); max_blocks 0 = default. */
 int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
-			     uint32_t *kernel_id);
+			     const char **kernel);
 /* ecg_csum_cells_ptrs: every cell of the table p->cells_dev (p->ncells entries). */
 int ecg_k_launch_csum_cells(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
-			    uint32_t *kernel_id);
+			    const char **kernel);
 /* Whether the device serves misaligned dword loads and stores (the unaligned
  * access mode the ROCm driver enables on gfx9+), which the product kernels
  * use for destinations off a dword boundary and for partial columns of
@@ -629,31 +619,29 @@ uint64_t ecg_k_copy_tiles(uint64_t dst, uint64_t len);
 int ecg_k_launch_fetch(const uint64_t *host_src, uint64_t *dst, uint32_t nwords, void *stream);
 /* One launch of ntiles workgroups over nseg segments (segs_dev in device memory). */
 int ecg_k_launch_copy_segs(const ecg_copy_seg_t *segs_dev, uint32_t nseg, uint64_t ntiles,
-			   void *stream, uint32_t *kernel_id);
+			   void *stream, const char **kernel);
 /* Implemented in kernels/ecg_kernels.hip.  Returns a hipError_t value. */
 int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg,
-			void *stream, uint32_t *kernel_id);
+			void *stream, const char **kernel);
 /* One-cell product with a per-stripe coefficient column (p->k == 1):
  * dst[s][r] = tbl[r][sel_dev[s]] * src[s]; tables for columns < ncols <= 16.
  * 16-byte aligned operands only (hipErrorInvalidValue otherwise). */
 int ecg_k_launch_matmul_sel(const ecg_mm_params_t *p, const uint8_t *sel_dev, uint32_t ncols,
-			    void *stream, uint32_t *kernel_id);
+			    void *stream, const char **kernel);
 /* Streaming kernels used only to measure the box's achievable HBM rates:
  * mode 0 copy, 1 read-only, 2 write-only. */
 int ecg_k_launch_copy(const void *src, void *dst, uint64_t bytes, int mode, void *stream,
-		      uint32_t max_blocks, uint32_t *kernel_id);
+		      uint32_t max_blocks, const char **kernel);
 /* Fused product + checksum (kernels/ecg_fused_kernels.hip).  Returns 1 (and
  * launches nothing) when the operands are not 16-byte aligned, or when
  * q->src_out is set and the shape has no SRC instantiation. */
 int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs_params_t *q,
-			     const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
+			     const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* Compare n checksums of len (2, 4 or 8) bytes: result[0] += mismatches,
  * result[1] = min(result[1], lowest mismatching index); the host presets
  * result to {0, UINT64_MAX} (kernels/ecg_csum_kernels.hip). */
 int ecg_k_launch_csum_compare(const void *got, const void *want, uint64_t n, uint32_t len,
-			      uint64_t *result, void *stream, uint32_t *kernel_id);
-#define ECG_KID_FUSED 500u	/* fused kernel ids start here (below ECG_KID_COPY_SEGS) */
-const char *ecg_k_fused_kernel_name(uint32_t kernel_id);
+			      uint64_t *result, void *stream, const char **kernel);
 /* The common alignment (16, 8, 4 or 1 bytes) of every cell address of a
  * product launch: the lane access granule the product kernels use. */
 uint32_t ecg_k_align_granule(const ecg_mm_params_t *p);
@@ -665,9 +653,7 @@ uint32_t ecg_k_align_granule(const ecg_mm_params_t *p);
  * misaligned, so they need the device's unaligned access mode); 0 = the
  * byte-granular kernel (ecg_ptrs.c ptr_granule). */
 int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t *cells_dev, int granule,
-			     const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id);
-#define ECG_KID_PTR 600u	/* pointer-table kernel ids start here */
-const char *ecg_k_ptr_kernel_name(uint32_t kernel_id);
+			     const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* Per-request delta updates through a pointer table (the batching queue's
  * device-cell aggregation updates, ecg_update_ptrs):  item s of the launch,
  * a record of ECG_UPD_REC(rows) uint64_t at items_dev + s * ECG_UPD_REC(rows):
@@ -684,12 +670,10 @@ const char *ecg_k_ptr_kernel_name(uint32_t kernel_id);
 #define ECG_UPD_MU 8
 #define ECG_UPD_REC(rows) ((rows) + 2 * ECG_UPD_MU + 2)
 int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t *items_dev, uint32_t ncols, int granule,
-			     void *stream, uint32_t *kernel_id);
+			     void *stream, const char **kernel);
 /* Chunked checksums (kernels/ecg_csum_kernels.hip). max_blocks 0 = default. */
 int ecg_k_launch_csum(const ecg_csum_params_t *p, void *stream, uint32_t max_blocks,
-		      uint32_t *kernel_id);
-const char *ecg_k_csum_kernel_name(uint32_t kernel_id);
-const char *ecg_k_kernel_name(uint32_t kernel_id);
+		      const char **kernel);
 #ifdef __cplusplus
 }
 #endif

@@ -338,16 +338,16 @@ int ecg_set_wg_per_cu(ecg_ctx_t *ctx, uint32_t wg_per_cu)
 /* ------------------------------------------------------------------------ */
 static int launch(ecg_ctx_t *ctx, const ecg_mm_params_t *prm, hipStream_t st)
 {
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e;
 
 	ecg_trace_push("ecg:launch");
-	e = ecg_tune_launch(ctx, prm, st, &kid);
+	e = ecg_tune_launch(ctx, prm, st, &kernel);
 	ecg_trace_pop();
 	if (e != 0)
 		return ecg_hip_fail((hipError_t)e, "kernel launch");
 	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	ecg_set_last_kernel(kernel);
 	return 0;
 }
 
@@ -440,7 +440,7 @@ int ecg_matmul_sel(ecg_ctx_t *ctx, int ncols, int rows, const unsigned char *coe
 		   int64_t dstride, void *stream)
 {
 	ecg_mm_params_t *prm;
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int rc, r, j, e;
 
 	if (ncols < 1 || ncols > ECG_KMAX_K || rows < 1 || rows > ECG_KMAX_R || coef == NULL ||
@@ -468,12 +468,12 @@ int ecg_matmul_sel(ecg_ctx_t *ctx, int ncols, int rows, const unsigned char *coe
 		for (j = 0; j < ncols; j++)
 			ecg_build_ptbl(coef[r * ncols + j], &prm->tbl[r][j]);
 	}
-	e = ecg_k_launch_matmul_sel(prm, sel_dev, (uint32_t)ncols, (void *)ecg_pick_stream(ctx, stream), &kid);
+	e = ecg_k_launch_matmul_sel(prm, sel_dev, (uint32_t)ncols, (void *)ecg_pick_stream(ctx, stream), &kernel);
 	free(prm);
 	if (e)
 		return ecg_hip_fail((hipError_t)e, "matmul_sel launch");
 	ECG_STAT_ADD(ctx, launches, 1);
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	ecg_set_last_kernel(kernel);
 	return 0;
 }
 
@@ -662,7 +662,8 @@ static int matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coe
 		goto two_pass_src;
 	if (fused) {
 		ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
-		uint32_t kid = 0;
+		/* rows == 0 (ecg_matmul_csum does not refuse it) launches nothing */
+		const char *kernel = ECG_NO_LAUNCH_KERNEL;
 		int e, j;
 
 		if (prm == NULL)
@@ -698,12 +699,12 @@ static int matmul_csum(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coe
 				return ecg_hip_fail(he, "csum memset");
 			}
 		}
-		e = ecg_k_launch_matmul_csum(prm, &q, &ctx->cfg, (void *)st, &kid);
+		e = ecg_k_launch_matmul_csum(prm, &q, &ctx->cfg, (void *)st, &kernel);
 		free(prm);
 		if (e == 0) {
 			ECG_STAT_ADD(ctx, launches, 1);
 			ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)(rows + (src_csums ? k : 0)) * S * q.nch);
-			ecg_set_last_kernel(ecg_k_kernel_name(kid));
+			ecg_set_last_kernel(kernel);
 			return 0;
 		}
 		if (e != 1)
@@ -1358,7 +1359,7 @@ int ecg_dev_copy_kernel(ecg_ctx_t *ctx, void *dst, const void *src, size_t bytes
 			void *stream)
 {
 	int rc = ecg_ctx_enter(ctx);
-	uint32_t kid = 0;
+	const char *kernel = ECG_NO_LAUNCH_KERNEL;	/* bytes < 16 launches nothing */
 	int e;
 
 	if (rc)
@@ -1366,9 +1367,9 @@ int ecg_dev_copy_kernel(ecg_ctx_t *ctx, void *dst, const void *src, size_t bytes
 	if (mode < 0 || mode > 2)
 		return ecg_fail(-ECG_DER_INVAL, "copy kernel: mode %d", mode);
 	e = ecg_k_launch_copy(src, dst, bytes, mode, (void *)ecg_pick_stream(ctx, stream),
-			      ctx->cfg.grid_x, &kid);
+			      ctx->cfg.grid_x, &kernel);
 	if (e)
 		return ecg_hip_fail((hipError_t)e, "copy kernel");
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	ecg_set_last_kernel(kernel);
 	return 0;
 }

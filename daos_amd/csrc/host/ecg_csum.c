@@ -614,7 +614,9 @@ int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_
 	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
 	const void *tbl;
 	uint64_t per, first_end;
-	uint32_t kid = 0;
+	/* an extent of 2^32 chunks has an nchunks of 0 (ecg_csum_chunk_count
+	 * returns 32 bits) and launches nothing */
+	const char *kernel = ECG_NO_LAUNCH_KERNEL;
 	int rc, e;
 
 	if (ctx == NULL || (n_ext && rx_nr && (buf == NULL || csums == NULL)) || rcs == 0)
@@ -677,8 +679,8 @@ int ecg_csum_extents(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_
 		prm.variant = 0;	/* adler32: the kernel picks by shape */
 	}
 	ecg_trace_push("ecg:csum_extents");
-	e = ecg_k_launch_csum(&prm, (void *)ecg_pick_stream(ctx, stream), ctx->csum_blocks, &kid);
-	rc = ecg_launch_done(ctx, e, "csum kernel launch", 1, ecg_k_kernel_name(kid));
+	e = ecg_k_launch_csum(&prm, (void *)ecg_pick_stream(ctx, stream), ctx->csum_blocks, &kernel);
+	rc = ecg_launch_done(ctx, e, "csum kernel launch", 1, kernel);
 	if (rc == 0)
 		ECG_STAT_ADD(ctx, csum_chunks, (uint64_t)prm.n_ext * prm.nchunks);
 	return rc;
@@ -742,7 +744,7 @@ int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want
 	const int cl = ecg_csum_len(type);
 	hipStream_t st;
 	hipError_t he;
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int rc, e;
 
 	if (cl < 0)
@@ -761,8 +763,8 @@ int ecg_csum_compare(ecg_ctx_t *ctx, int type, const void *got, const void *want
 	if (n == 0)
 		return 0;
 	ecg_trace_push("ecg:csum_compare");
-	e = ecg_k_launch_csum_compare(got, want, n, (uint32_t)cl, result, (void *)st, &kid);
-	return ecg_launch_done(ctx, e, "csum_compare kernel launch", 1, ecg_k_kernel_name(kid));
+	e = ecg_k_launch_csum_compare(got, want, n, (uint32_t)cl, result, (void *)st, &kernel);
+	return ecg_launch_done(ctx, e, "csum_compare kernel launch", 1, kernel);
 }
 
 int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
@@ -771,7 +773,7 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 		  uint32_t first_cell, uint32_t *masks, void *stream)
 {
 	const int cl = ecg_csum_len(type);
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int rc, e;
 
 	if (cl != 2 && cl != 4 && cl != 8)
@@ -792,8 +794,8 @@ int ecg_csum_mask(ecg_ctx_t *ctx, int type, const void *got, const void *want,
 		return 0;
 	ecg_trace_push("ecg:csum_mask");
 	e = ecg_k_launch_csum_mask(got, want, nstripes, ncells, nch, stripe_stride, cell_stride, first_cell,
-				   (uint32_t)cl, masks, (void *)ecg_pick_stream(ctx, stream), &kid);
-	return ecg_launch_done(ctx, e, "csum_mask kernel launch", 1, ecg_k_kernel_name(kid));
+				   (uint32_t)cl, masks, (void *)ecg_pick_stream(ctx, stream), &kernel);
+	return ecg_launch_done(ctx, e, "csum_mask kernel launch", 1, kernel);
 }
 
 /* [a, a + alen) and [b, b + blen) share a byte */
@@ -870,7 +872,7 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const void *tbl, const struct
 			 int bytewise, const uint32_t *masks, unsigned which, void *csums, void *result, hipStream_t st)
 {
 	ecg_csum_masked_params_t prm;
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e;
 
 	memset(&prm, 0, sizeof(prm));
@@ -892,9 +894,9 @@ static int masked_launch(ecg_ctx_t *ctx, int type, const void *tbl, const struct
 	prm.slots = (which & ECG_CM_ERASED ? (uint32_t)p : 0) + (which & ECG_CM_SURVIVORS ? (uint32_t)k : 0);
 	prm.type = (uint32_t)type;
 	ecg_trace_push(cells_dev ? "ecg:csum_masked_ptrs" : "ecg:csum_masked");
-	e = ecg_k_launch_csum_masked(&prm, (void *)st, ctx->csum_blocks, &kid);
+	e = ecg_k_launch_csum_masked(&prm, (void *)st, ctx->csum_blocks, &kernel);
 	return ecg_launch_done(ctx, e, cells_dev ? "csum_masked_ptrs kernel launch" : "csum_masked kernel launch", 1,
-			       ecg_k_kernel_name(kid));
+			       kernel);
 }
 
 /* ECG_RM_SPARSE is accepted and ignored: the one grid serves dense and clean
@@ -1070,7 +1072,7 @@ int ecg_csum_cells_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t r
 	struct ecg_staged t;
 	const void *tbl;
 	uint64_t nch, bytes;
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	hipStream_t st;
 	int rc, e;
 
@@ -1117,8 +1119,8 @@ int ecg_csum_cells_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t r
 	prm.nch = (uint32_t)nch;
 	prm.type = (uint32_t)type;
 	ecg_trace_push("ecg:csum_cells_ptrs");
-	e = ecg_k_launch_csum_cells(&prm, (void *)st, ctx->csum_blocks, &kid);
-	rc = ecg_launch_done(ctx, e, "csum_cells_ptrs kernel launch", 1, ecg_k_kernel_name(kid));
+	e = ecg_k_launch_csum_cells(&prm, (void *)st, ctx->csum_blocks, &kernel);
+	rc = ecg_launch_done(ctx, e, "csum_cells_ptrs kernel launch", 1, kernel);
 	rc = ecg_staged_close(ctx, &t, st, rc);
 	if (rc == 0)
 		ECG_STAT_ADD(ctx, csum_chunks, ncells * nch);

@@ -110,6 +110,12 @@ int ecg_hip_fail(hipError_t e, const char *what);
  * profiles/r01/pcie.json). */
 hipError_t ecg_stage_copy(void *dst, const void *src, size_t bytes, size_t row, hipMemcpyKind kind,
 			  hipStream_t st);
+/* name: never NULL.  A launcher that finds nothing to launch succeeds and
+ * reports no kernel (ecg_kabi.h); almost every caller has returned before that
+ * can happen.  The few whose checks let an empty launch through start from
+ * ECG_NO_LAUNCH_KERNEL: what ecg_last_kernel() has always shown after such a
+ * call (the first product kernel's name), kept until those calls are fixed. */
+#define ECG_NO_LAUNCH_KERNEL "ecg_mm_kernel<2,1,0,0>"
 void ecg_set_last_kernel(const char *name);
 
 /* GF(2^8) tables (ecg_gf.c) */
@@ -275,7 +281,7 @@ int ecg_trace_active(void);
 struct ecg_tuner;
 int ecg_tune_init(ecg_ctx_t *ctx);
 void ecg_tune_fini(ecg_ctx_t *ctx);
-int ecg_tune_launch(ecg_ctx_t *ctx, const ecg_mm_params_t *p, hipStream_t st, uint32_t *kid);
+int ecg_tune_launch(ecg_ctx_t *ctx, const ecg_mm_params_t *p, hipStream_t st, const char **kernel);
 /* The device whose memory p is; < 0 for host memory: ECG_PTR_HOST (known to
  * the HIP runtime: pinned, registered, managed) or ECG_PTR_UNKNOWN (plain
  * malloc / mmap) (ecg_stage.c). */
@@ -288,14 +294,16 @@ int ecg_ptr_device(const void *p);
 int ecg_ptr_device_cached(const void *p);
 /* The same for any launcher of the product (the pointer-table kernel): `g`
  * its lane granule, `layout` its layout class (ECG_TUNE_LAYOUT_*), `fn(p,
- * cfg, stream, kid, arg)` the launch under a given geometry. */
+ * cfg, stream, kernel, arg)` the launch under a given geometry, which reports
+ * the kernel it launched as the ecg_k_launch_* do (every path here calls fn
+ * exactly once). */
 typedef int (*ecg_mm_launch_fn)(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, void *stream,
-				uint32_t *kid, const void *arg);
+				const char **kernel, const void *arg);
 #define ECG_TUNE_LAYOUT_SEPARATE 0u	/* source and destination stripe strides differ */
 #define ECG_TUNE_LAYOUT_INTERLEAVED 1u	/* one stripe stride: in-place recovery */
 #define ECG_TUNE_LAYOUT_PTRS 2u		/* per-stripe pointer table */
 int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uint32_t layout,
-		       ecg_mm_launch_fn fn, const void *arg, hipStream_t st, uint32_t *kid);
+		       ecg_mm_launch_fn fn, const void *arg, hipStream_t st, const char **kernel);
 
 /* synchronous one-stripe product on ctx's GPU; place = ecg_cells_place's
  * placement of the k + rows cells (NULL: all host memory) (ecg_stage.c) */

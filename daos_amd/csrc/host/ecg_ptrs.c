@@ -201,19 +201,19 @@ struct ptr_launch_arg {
 	int granule;
 };
 
-static int launch_ptrs(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kid,
+static int launch_ptrs(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, void *stream, const char **kernel,
 		       const void *arg)
 {
 	const struct ptr_launch_arg *a = arg;
 
-	return ecg_k_launch_matmul_ptrs(p, a->cells_dev, a->granule, cfg, stream, kid);
+	return ecg_k_launch_matmul_ptrs(p, a->cells_dev, a->granule, cfg, stream, kernel);
 }
 
 /* The product over the table a->cells_dev, through the launch tuner like the
  * strided product: wide stripes probe the blocks-per-CU cap per (shape,
  * pointer-table layout). */
 static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k, int rows, const unsigned char *coef,
-			  uint64_t C, uint32_t S, hipStream_t st, uint32_t *kid)
+			  uint64_t C, uint32_t S, hipStream_t st, const char **kernel)
 {
 	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
 	int ke;
@@ -228,7 +228,7 @@ static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k,
 	for (int r = 0; r < rows; r++)
 		for (int j = 0; j < k; j++)
 			ecg_build_ptbl(coef[(size_t)r * k + j], &prm->tbl[r][j]);
-	ke = ecg_tune_launch_fn(ctx, prm, (uint32_t)a->granule, ECG_TUNE_LAYOUT_PTRS, launch_ptrs, a, st, kid);
+	ke = ecg_tune_launch_fn(ctx, prm, (uint32_t)a->granule, ECG_TUNE_LAYOUT_PTRS, launch_ptrs, a, st, kernel);
 	free(prm);
 	return ke ? ecg_hip_fail((hipError_t)ke, "pointer-table kernel launch") : 0;
 }
@@ -244,7 +244,7 @@ static int launch_table(ecg_ctx_t *ctx, struct ecg_scratch_slot *sc, int k, int 
 	const struct ptr_launch_arg a = {sc->dev,
 					 ptr_granule((const uint64_t *)sc->pin, S, k, rows, (int)ctx->cfg.no_unaligned)};
 	size_t tbytes = (size_t)S * (size_t)(k + rows) * sizeof(uint64_t);
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int rc, done;
 
 	if (!(gather && gather->n)) {	/* no gather copies: maybe the offset kernel's layout */
@@ -261,10 +261,10 @@ static int launch_table(ecg_ctx_t *ctx, struct ecg_scratch_slot *sc, int k, int 
 	if (gather && gather->n)
 		rc = ecg_segs_launch(gather, (unsigned char *)sc->dev + seg_off, st);
 	if (rc == 0)
-		rc = launch_product(ctx, &a, k, rows, coef, C, S, st, &kid);
+		rc = launch_product(ctx, &a, k, rows, coef, C, S, st, &kernel);
 	rc = ecg_table_done(sc, st, rc);
 	if (rc == 0)
-		ecg_set_last_kernel(ecg_k_kernel_name(kid));
+		ecg_set_last_kernel(kernel);
 	return rc;
 }
 
@@ -540,7 +540,8 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 	struct ecg_scratch_slot *sc = NULL;
 	ecg_mm_params_t *prm = NULL;
 	uint64_t bits = C;
-	uint32_t nit = 0, nset = 0, nwave = 0, kid = 0;
+	uint32_t nit = 0, nset = 0, nwave = 0;
+	const char *kernel = NULL;
 	hipStream_t st;
 	int rc = 0, overlap = 0, granule;
 
@@ -670,7 +671,7 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 				cnt += it[i].wave == w;
 			prm->nstripes = cnt;
 			ke = ecg_k_launch_update_ptrs(prm, (const uint64_t *)sc->dev + (size_t)at * rec, (uint32_t)k,
-						      granule, (void *)st, &kid);
+						      granule, (void *)st, &kernel);
 			if (ke != 0)
 				rc = ecg_hip_fail((hipError_t)ke, "update_ptrs kernel launch");
 			at += cnt;
@@ -690,7 +691,7 @@ int ecg_update_ptrs_coef(ecg_ctx_t *ctx, int k, int rows, const unsigned char *c
 		ECG_STAT_ADD(ctx, launches, nwave);
 		ECG_STAT_ADD(ctx, update_cells, nreq);
 		ECG_STAT_ADD(ctx, update_bytes, (uint64_t)nreq * C);
-		ecg_set_last_kernel(ecg_k_kernel_name(kid));
+		ecg_set_last_kernel(kernel);
 		if (nlaunch)
 			*nlaunch = nwave;
 	}

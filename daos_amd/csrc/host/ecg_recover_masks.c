@@ -164,7 +164,7 @@ int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int
 {
 	const int ptrs = cells_dev != NULL;
 	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e;
 
 	if (prm == NULL)
@@ -181,10 +181,10 @@ int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int
 	ecg_trace_push(ptrs ? "ecg:recover_masks_ptrs" : "ecg:recover_masks");
 	e = ecg_k_launch_recover_masks(prm, settbl, cells_dev, masks, (uint64_t *)result,
 				       ctx->cfg.variant == 2 || bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg,
-				       (void *)st, &kid);
+				       (void *)st, &kernel);
 	free(prm);
 	return ecg_launch_done(ctx, e, ptrs ? "recover_masks_ptrs kernel launch" : "recover_masks kernel launch", 1,
-			       ecg_k_recover_masks_kernel_name(kid));
+			       kernel);
 }
 
 int ecg_recover_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,

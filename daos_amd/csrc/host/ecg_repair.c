@@ -97,15 +97,15 @@ static int repair_launch(ecg_ctx_t *ctx, const char *fn, const ecg_mm_params_t *
 			 const uint64_t *cells_dev, int bytewise, const uint32_t *status, void *result, hipStream_t st)
 {
 	char what[48];
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e;
 
 	snprintf(what, sizeof(what), "ecg:%s", fn);
 	ecg_trace_push(what);
 	e = ecg_k_launch_repair(prm, rowtbl, cells_dev, status, (uint64_t *)result, ctx->cfg.variant == 2 || bytewise,
-				&ctx->cfg, (void *)st, &kid);
+				&ctx->cfg, (void *)st, &kernel);
 	snprintf(what, sizeof(what), "%s kernel launch", fn);
-	return ecg_launch_done(ctx, e, what, 1, ecg_k_repair_kernel_name(kid));
+	return ecg_launch_done(ctx, e, what, 1, kernel);
 }
 
 int ecg_repair(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,

@@ -54,7 +54,7 @@ void ecg_segs_fini(struct ecg_segs *v)
 
 int ecg_segs_launch(const struct ecg_segs *v, const void *segs_dev, hipStream_t st)
 {
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int ke;
 
 	if (v->n == 0)
@@ -62,10 +62,10 @@ int ecg_segs_launch(const struct ecg_segs *v, const void *segs_dev, hipStream_t 
 	if (v->n > UINT32_MAX)
 		return ecg_fail(-ECG_DER_INVAL, "copy segments: %zu segments", v->n);
 	ke = ecg_k_launch_copy_segs((const ecg_copy_seg_t *)segs_dev, (uint32_t)v->n, v->tiles, (void *)st,
-				    &kid);
+				    &kernel);
 	if (ke != 0)
 		return ecg_hip_fail((hipError_t)ke, "segment copy launch");
-	ecg_set_last_kernel(ecg_k_kernel_name(kid));
+	ecg_set_last_kernel(kernel);
 	return 0;
 }
 

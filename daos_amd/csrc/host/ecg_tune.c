@@ -289,20 +289,20 @@ static int make_events(struct ecg_tune_ent *e)
 	return 0;
 }
 
-static int launch_offsets(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kid,
+static int launch_offsets(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, void *stream, const char **kernel,
 			  const void *arg)
 {
 	(void)arg;
-	return ecg_k_launch_matmul(p, cfg, stream, kid);
+	return ecg_k_launch_matmul(p, cfg, stream, kernel);
 }
 
-int ecg_tune_launch(ecg_ctx_t *ctx, const ecg_mm_params_t *p, hipStream_t st, uint32_t *kid)
+int ecg_tune_launch(ecg_ctx_t *ctx, const ecg_mm_params_t *p, hipStream_t st, const char **kernel)
 {
-	return ecg_tune_launch_fn(ctx, p, ecg_k_align_granule(p), layout_class(p), launch_offsets, NULL, st, kid);
+	return ecg_tune_launch_fn(ctx, p, ecg_k_align_granule(p), layout_class(p), launch_offsets, NULL, st, kernel);
 }
 
 int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uint32_t layout,
-		       ecg_mm_launch_fn fn, const void *arg, hipStream_t st, uint32_t *kid)
+		       ecg_mm_launch_fn fn, const void *arg, hipStream_t st, const char **kernel)
 {
 	struct ecg_tuner *t = ctx->tuner;
 	ecg_launch_cfg_t cfg = ctx->cfg;
@@ -314,20 +314,20 @@ int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uin
 	cand = candidate_cap(p);
 	if (t == NULL || cand == 0 || cfg.wg_per_cu != 0 || cfg.variant != 0 || cfg.order != 0 ||
 	    cfg.grid_x != 0 || cfg.grid_y != 0)
-		return fn(p, &ctx->cfg, (void *)st, kid, arg);
+		return fn(p, &ctx->cfg, (void *)st, kernel, arg);
 	if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone)
-		return fn(p, &ctx->cfg, (void *)st, kid, arg);
+		return fn(p, &ctx->cfg, (void *)st, kernel, arg);
 
 	pthread_mutex_lock(&t->lock);
 	if (!enabled(t)) {
 		pthread_mutex_unlock(&t->lock);
-		return fn(p, &ctx->cfg, (void *)st, kid, arg);
+		return fn(p, &ctx->cfg, (void *)st, kernel, arg);
 	}
 	e = lookup(t, p, g, layout, 1);
 	if (e == NULL) {		/* probe budget spent: untuned shapes run uncapped */
 		cfg.wg_per_cu = ECG_WG_UNCAPPED;
 		pthread_mutex_unlock(&t->lock);
-		return fn(p, &cfg, (void *)st, kid, arg);
+		return fn(p, &cfg, (void *)st, kernel, arg);
 	}
 	if (e->n == 0 && !e->decided) {
 		e->stream = st;		/* the probe runs on the stream that starts it */
@@ -338,7 +338,7 @@ int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uin
 	if (e->decided) {
 		cfg.wg_per_cu = e->choice;
 		pthread_mutex_unlock(&t->lock);
-		return fn(p, &cfg, (void *)st, kid, arg);
+		return fn(p, &cfg, (void *)st, kernel, arg);
 	}
 	if (e->n < ECG_TUNE_PROBE && st != e->stream && ++e->stall >= ECG_TUNE_STALL) {
 		/* the probe's stream went quiet: start over on this one (events of
@@ -352,14 +352,14 @@ int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uin
 		/* timings still in flight, or another stream: run uncapped */
 		cfg.wg_per_cu = ECG_WG_UNCAPPED;
 		pthread_mutex_unlock(&t->lock);
-		return fn(p, &cfg, (void *)st, kid, arg);
+		return fn(p, &cfg, (void *)st, kernel, arg);
 	}
 	if (!e->events && make_events(e)) {
 		e->decided = 1;
 		e->choice = ECG_WG_UNCAPPED;
 		cfg.wg_per_cu = ECG_WG_UNCAPPED;
 		pthread_mutex_unlock(&t->lock);
-		return fn(p, &cfg, (void *)st, kid, arg);
+		return fn(p, &cfg, (void *)st, kernel, arg);
 	}
 	/* probing: arm 0 uncapped, arm 1 capped, each W untimed + T timed, back
 	 * to back; the lock is held across the timed launch so concurrent callers
@@ -374,7 +374,7 @@ int ecg_tune_launch_fn(ecg_ctx_t *ctx, const ecg_mm_params_t *p, uint32_t g, uin
 		timed = hipEventRecord(e->ev[arm][idx][0], st) == hipSuccess;
 		e->blocks[arm][idx] = mm_blocks(p);
 	}
-	rc = fn(p, &cfg, (void *)st, kid, arg);
+	rc = fn(p, &cfg, (void *)st, kernel, arg);
 	if (timed && (rc != 0 || hipEventRecord(e->ev[arm][idx][1], st) != hipSuccess)) {
 		e->decided = 1;		/* give up on this shape: uncapped */
 		e->choice = ECG_WG_UNCAPPED;

@@ -84,7 +84,7 @@ static int um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, u
 	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
 	const int ptrs = cells_dev != NULL;
 	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e, r, j;
 
 	if (prm == NULL)
@@ -116,11 +116,11 @@ static int um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, u
 	ecg_trace_push(ptrs ? "ecg:update_masks_ptrs" : "ecg:update_masks");
 	e = ecg_k_launch_update_masks(prm, cells_dev, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0,
 				      ctx->cfg.variant == 2 || bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg,
-				      (void *)st, &kid);
+				      (void *)st, &kernel);
 	free(prm);
 	/* update_cells / update_bytes stay: the count is known on the device only */
 	return ecg_launch_done(ctx, e, ptrs ? "update_masks_ptrs kernel launch" : "update_masks kernel launch", 1,
-			       ecg_k_update_masks_kernel_name(kid));
+			       kernel);
 }
 
 int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,

@@ -100,17 +100,18 @@ int ecg_verify_launch(ecg_ctx_t *ctx, const char *fn, const ecg_mm_params_t *prm
 		      int bytewise, uint32_t *status, void *result, hipStream_t st)
 {
 	char what[48];
-	uint32_t kid = 0;
+	const char *kernel = NULL;
 	int e;
 
 	snprintf(what, sizeof(what), "ecg:%s", fn);
 	ecg_trace_push(what);
-	e = ecg_k_launch_verify(prm, cells_dev, status, ctx->cfg.variant == 2 || bytewise, &ctx->cfg, (void *)st, &kid);
+	e = ecg_k_launch_verify(prm, cells_dev, status, ctx->cfg.variant == 2 || bytewise, &ctx->cfg, (void *)st,
+				&kernel);
 	if (e == 0)
 		e = ecg_k_launch_verify_summary(status, prm->nstripes, (int)prm->k, (int)prm->rows, (uint64_t *)result,
 						(void *)st);
 	snprintf(what, sizeof(what), "%s kernel launch", fn);
-	return ecg_launch_done(ctx, e, what, 2, ecg_k_verify_kernel_name(kid));
+	return ecg_launch_done(ctx, e, what, 2, kernel);
 }
 
 int ecg_verify(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,

@@ -183,7 +183,7 @@ extern "C" uint64_t ecg_k_copy_tiles(uint64_t dst, uint64_t len)
 }
 
 extern "C" int ecg_k_launch_copy_segs(const ecg_copy_seg_t *segs_dev, uint32_t nseg, uint64_t ntiles,
-				      void *stream, uint32_t *kernel_id)
+				      void *stream, const char **kernel)
 {
 	if (nseg == 0 || ntiles == 0)
 		return (int)hipSuccess;
@@ -191,7 +191,7 @@ extern "C" int ecg_k_launch_copy_segs(const ecg_copy_seg_t *segs_dev, uint32_t n
 		return (int)hipErrorInvalidValue;
 	hipLaunchKernelGGL(ecg_copy_segs_kernel, dim3((uint32_t)ntiles), dim3(CP_BLOCK), 0, (hipStream_t)stream,
 			   segs_dev, nseg);
-	if (kernel_id)
-		*kernel_id = ECG_KID_COPY_SEGS;
+	if (kernel)
+		*kernel = "ecg_copy_segs_kernel";
 	return (int)hipGetLastError();
 }

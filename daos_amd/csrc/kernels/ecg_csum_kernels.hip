@@ -838,7 +838,7 @@ ecg_csum_mask_kernel(const uint8_t *got, const uint8_t *want, uint32_t nstripes,
 }
 
 // One table per kernel family, a row per (hash type, 16-byte aligned or not);
-// a kernel's id is its table's first id plus its row.  One table kind per
+// the launcher reports the row's name.  One table kind per
 // kernel: the nibble tables for 16-byte aligned chunks, the 5-bit tables for
 // the byte-granular kernels.
 template <class P>
@@ -908,49 +908,19 @@ const csum_entry<ecg_csum_masked_params_t> g_cells_ptr[] = {
 	{7, false, ecg_adler_cells_ptr_kernel<false>, "ecg_adler_cells_ptr_kernel<bytes>"},
 };
 
-template <class E, uint32_t N>
-constexpr uint32_t rows(const E (&)[N])
-{
-	return N;
-}
-constexpr uint32_t KID_SPLIT = ECG_KID_CSUM + rows(g_csum);
-constexpr uint32_t KID_GROUP = KID_SPLIT + rows(g_split);
-constexpr uint32_t KID_COMPARE = KID_GROUP + rows(g_group);
-constexpr uint32_t KID_MASK = KID_COMPARE + 1;
-constexpr uint32_t KID_MASKED = KID_MASK + 1;
-constexpr uint32_t KID_MASKED_PTR = KID_MASKED + rows(g_masked);
-constexpr uint32_t KID_CELLS_PTR = KID_MASKED_PTR + rows(g_masked_ptr);
-
-template <auto &T>
-const char *row_name(uint32_t i)
-{
-	return T[i].name;
-}
-const struct {
-	uint32_t first, n;
-	const char *(*name)(uint32_t row);
-} g_ids[] = {
-	{ECG_KID_CSUM, rows(g_csum), row_name<g_csum>},
-	{KID_SPLIT, rows(g_split), row_name<g_split>},
-	{KID_GROUP, rows(g_group), row_name<g_group>},
-	{KID_MASKED, rows(g_masked), row_name<g_masked>},
-	{KID_MASKED_PTR, rows(g_masked_ptr), row_name<g_masked_ptr>},
-	{KID_CELLS_PTR, rows(g_cells_ptr), row_name<g_cells_ptr>},
-};
-
-// Launch the (type, aligned) row of table t, whose ids start at `first`, on
-// min(nb, cap) blocks of `threads` and report its id.
+// Launch the (type, aligned) row of table t on min(nb, cap) blocks of `threads`
+// and report its name.
 template <class P, uint32_t N>
-int launch_row(const csum_entry<P> (&t)[N], uint32_t first, bool aligned, uint64_t nb, uint64_t cap,
-	       uint32_t threads, const P *p, void *stream, uint32_t *kernel_id)
+int launch_row(const csum_entry<P> (&t)[N], bool aligned, uint64_t nb, uint64_t cap, uint32_t threads, const P *p,
+	       void *stream, const char **kernel)
 {
 	for (uint32_t i = 0; i < N; i++) {
 		if (t[i].type != p->type || t[i].aligned != aligned)
 			continue;
 		hipLaunchKernelGGL(t[i].fn, dim3((uint32_t)(nb < cap ? nb : cap)), dim3(threads), 0,
 				   (hipStream_t)stream, *p);
-		if (kernel_id)
-			*kernel_id = first + i;
+		if (kernel)
+			*kernel = t[i].name;
 		return (int)hipGetLastError();
 	}
 	return (int)hipErrorInvalidValue;
@@ -959,7 +929,7 @@ int launch_row(const csum_entry<P> (&t)[N], uint32_t first, bool aligned, uint64
 } // namespace
 
 extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
-					uint32_t *kernel_id)
+					const char **kernel)
 {
 	const uint64_t total = (uint64_t)p->nstripes * p->slots * p->nch;
 	const bool ptrs = p->cells_dev != nullptr;
@@ -978,14 +948,14 @@ extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void 
 		return (int)hipErrorInvalidValue;
 	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
 	if (ptrs)
-		return launch_row(g_masked_ptr, KID_MASKED_PTR, aligned, (total + CS_WAVES - 1) / CS_WAVES,
-				  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
-	return launch_row(g_masked, KID_MASKED, aligned, (total + CS_WAVES - 1) / CS_WAVES,
-			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
+		return launch_row(g_masked_ptr, aligned, (total + CS_WAVES - 1) / CS_WAVES,
+				  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel);
+	return launch_row(g_masked, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks ? max_blocks : 256 * 16,
+			  CS_BLOCK, p, stream, kernel);
 }
 
 extern "C" int ecg_k_launch_csum_cells(const ecg_csum_masked_params_t *p, void *stream, uint32_t max_blocks,
-				       uint32_t *kernel_id)
+				       const char **kernel)
 {
 	uint64_t total;
 
@@ -996,14 +966,14 @@ extern "C" int ecg_k_launch_csum_cells(const ecg_csum_masked_params_t *p, void *
 	    __builtin_mul_overflow(p->ncells, (uint64_t)p->nch, &total) ||
 	    (!p->bytewise && ((p->cell_bytes | p->chunk_bytes) & 15u)))
 		return (int)hipErrorInvalidValue;
-	return launch_row(g_cells_ptr, KID_CELLS_PTR, !p->bytewise, (total + CS_WAVES - 1) / CS_WAVES,
-			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel_id);
+	return launch_row(g_cells_ptr, !p->bytewise, (total + CS_WAVES - 1) / CS_WAVES,
+			  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel);
 }
 
 extern "C" int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_t nstripes, uint32_t ncells,
 				      uint32_t nch, uint64_t stripe_stride, uint64_t cell_stride,
 				      uint32_t first_cell, uint32_t len, uint32_t *masks, void *stream,
-				      uint32_t *kernel_id)
+				      const char **kernel)
 {
 	const uint64_t n = (uint64_t)nstripes * ncells;
 	uint64_t nb = (n + CS_BLOCK - 1) / CS_BLOCK;
@@ -1020,13 +990,13 @@ extern "C" int ecg_k_launch_csum_mask(const void *got, const void *want, uint32_
 		return (int)hipErrorInvalidValue;
 	hipLaunchKernelGGL(fn, dim3((uint32_t)nb), dim3(CS_BLOCK), 0, (hipStream_t)stream, (const uint8_t *)got,
 			   (const uint8_t *)want, nstripes, ncells, nch, stripe_stride, cell_stride, first_cell, masks);
-	if (kernel_id)
-		*kernel_id = KID_MASK;
+	if (kernel)
+		*kernel = "ecg_csum_mask_kernel";
 	return (int)hipGetLastError();
 }
 
 extern "C" int ecg_k_launch_csum_compare(const void *got, const void *want, uint64_t n, uint32_t len,
-					 uint64_t *result, void *stream, uint32_t *kernel_id)
+					 uint64_t *result, void *stream, const char **kernel)
 {
 	uint64_t nb = (n + CS_BLOCK - 1) / CS_BLOCK;
 
@@ -1041,25 +1011,13 @@ extern "C" int ecg_k_launch_csum_compare(const void *got, const void *want, uint
 		return (int)hipErrorInvalidValue;
 	hipLaunchKernelGGL(fn, dim3((uint32_t)nb), dim3(CS_BLOCK), 0, (hipStream_t)stream, (const uint8_t *)got,
 			   (const uint8_t *)want, n, (unsigned long long *)result);
-	if (kernel_id)
-		*kernel_id = KID_COMPARE;
+	if (kernel)
+		*kernel = "ecg_csum_compare_kernel";
 	return (int)hipGetLastError();
 }
 
-extern "C" const char *ecg_k_csum_kernel_name(uint32_t id)
-{
-	if (id == KID_COMPARE)
-		return "ecg_csum_compare_kernel";
-	if (id == KID_MASK)
-		return "ecg_csum_mask_kernel";
-	for (const auto &r : g_ids)
-		if (id >= r.first && id < r.first + r.n)
-			return r.name(id - r.first);
-	return "?";
-}
-
 extern "C" int ecg_k_launch_csum(const ecg_csum_params_t *p, void *stream, uint32_t max_blocks,
-				 uint32_t *kernel_id)
+				 const char **kernel)
 {
 	const uint64_t total = (uint64_t)p->n_ext * p->nchunks;
 	const bool aligned = (((uint64_t)(uintptr_t)p->src | (uint64_t)p->ext_stride | p->first_bytes |
@@ -1073,16 +1031,15 @@ extern "C" int ecg_k_launch_csum(const ecg_csum_params_t *p, void *stream, uint3
 	if (total == 0)
 		return (int)hipSuccess;
 	if (aligned && split)
-		return launch_row(g_split, KID_SPLIT, true, total, max_blocks ? max_blocks : 256 * 8, 64 * SPLIT_NW, p,
-				  stream, kernel_id);
+		return launch_row(g_split, true, total, max_blocks ? max_blocks : 256 * 8, 64 * SPLIT_NW, p, stream,
+				  kernel);
 	if (max_blocks == 0)
 		max_blocks = 256 * 16;	// 16 blocks per CU, grid-stride beyond
 	if (p->type != 7 && aligned && p->variant == 3) {
 		const uint32_t per_block = CS_WAVES * (64 / ECG_CSUM_GLANES);
 
-		return launch_row(g_group, KID_GROUP, true, (total + per_block - 1) / per_block, max_blocks, CS_BLOCK, p,
-				  stream, kernel_id);
+		return launch_row(g_group, true, (total + per_block - 1) / per_block, max_blocks, CS_BLOCK, p, stream,
+				  kernel);
 	}
-	return launch_row(g_csum, ECG_KID_CSUM, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks, CS_BLOCK, p,
-			  stream, kernel_id);
+	return launch_row(g_csum, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks, CS_BLOCK, p, stream, kernel);
 }

@@ -552,17 +552,9 @@ static const csentry g_cskernels[] = {
 	CSS3(0, 0),
 };
 #define N_CSKERNELS ((uint32_t)(sizeof(g_cskernels) / sizeof(g_cskernels[0])))
-#define KID_FUSED ECG_KID_FUSED	/* fused kernel ids: KID_FUSED + index */
-
-extern "C" const char *ecg_k_fused_kernel_name(uint32_t id)
-{
-	if (id >= KID_FUSED && id < KID_FUSED + N_CSKERNELS)
-		return g_cskernels[id - KID_FUSED].name;
-	return "?";
-}
 
 extern "C" int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs_params_t *q,
-				       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+				       const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	const bool src = q->src_out != nullptr;
 	uint32_t id = N_CSKERNELS;
@@ -608,7 +600,7 @@ extern "C" int ecg_k_launch_matmul_csum(const ecg_mm_params_t *p, const ecg_mmcs
 	if (gy > 65535)
 		gy = 65535;
 	hipLaunchKernelGGL(g_cskernels[id].fn, dim3(gx, gy), dim3(BLOCK), 0, (hipStream_t)stream, *p, *q);
-	if (kernel_id)
-		*kernel_id = KID_FUSED + id;
+	if (kernel)
+		*kernel = g_cskernels[id].name;
 	return (int)hipGetLastError();
 }

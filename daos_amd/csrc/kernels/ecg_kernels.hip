@@ -271,16 +271,6 @@ static const kentry g_kernels[] = {
 };
 #define N_KERNELS ((uint32_t)(sizeof(g_kernels) / sizeof(g_kernels[0])))
 
-
-
-
-#define KID_SEL 700u		/* per-stripe column kernels: <1>, <2>, <0> */
-
-#define KID_BYTE N_KERNELS
-#define KID_COPY (N_KERNELS + 1)
-#define KID_READ (N_KERNELS + 2)
-#define KID_WRITE (N_KERNELS + 3)
-
 // All output cells equally far (md bytes) past a dword boundary: *head = the
 // 4 - md bytes before their first aligned dword (1).  0 if they differ.
 // 4 lanes copy a dword from in + 1 + 4i to out + 3 + 4i: misaligned vector
@@ -372,38 +362,8 @@ extern "C" uint32_t ecg_k_align_granule(const ecg_mm_params_t *p)
 	return align_granule(p);
 }
 
-extern "C" const char *ecg_k_kernel_name(uint32_t id)
-{
-	if (id < N_KERNELS)
-		return g_kernels[id].name;
-	if (id == KID_BYTE)
-		return "ecg_mm_byte_kernel";
-	if (id == KID_COPY)
-		return "ecg_stream_kernel<copy>";
-	if (id == KID_READ)
-		return "ecg_stream_kernel<read>";
-	if (id == KID_WRITE)
-		return "ecg_stream_kernel<write>";
-	if (id >= ECG_KID_CSUM)
-		return ecg_k_csum_kernel_name(id);
-	if (id >= ECG_KID_FUSED && id < ECG_KID_FUSED + 100u)	/* below KID_PTR */
-		return ecg_k_fused_kernel_name(id);
-	if (id >= ECG_KID_PTR && id < ECG_KID_PTR + 100u)
-		return ecg_k_ptr_kernel_name(id);
-	if (id == ECG_KID_COPY_SEGS)
-		return "ecg_copy_segs_kernel";
-	if (id == KID_SEL)
-		return "ecg_mm_sel_kernel<1>";
-	if (id == KID_SEL + 1)
-		return "ecg_mm_sel_kernel<2>";
-	if (id == KID_SEL + 2)
-		return "ecg_mm_sel_kernel<0>";
-
-	return "?";
-}
-
 extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg,
-				   void *stream, uint32_t *kernel_id)
+				   void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
 	const uint32_t variant = cfg ? cfg->variant : 0;
@@ -424,8 +384,8 @@ extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cf
 		g = 2;		// k = 8, sources off a 16-byte boundary: funnel-shifted 16-byte lanes
 	if (variant == 2 || g == 0) {
 		hipLaunchKernelGGL(ecg_mm_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p);
-		if (kernel_id)
-			*kernel_id = KID_BYTE;
+		if (kernel)
+			*kernel = "ecg_mm_byte_kernel";
 		return (int)hipGetLastError();
 	}
 
@@ -464,8 +424,8 @@ extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cf
 
 		q.order = order;
 		hipLaunchKernelGGL(g_kernels[id].fn, dim3(gx), dim3(BLOCK), 0, st, q);
-		if (kernel_id)
-			*kernel_id = id;
+		if (kernel)
+			*kernel = g_kernels[id].name;
 		return (int)hipGetLastError();
 	}
 	uint32_t gx, gy;
@@ -480,13 +440,13 @@ extern "C" int ecg_k_launch_matmul(const ecg_mm_params_t *p, const ecg_launch_cf
 	} else {
 		hipLaunchKernelGGL(g_kernels[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p);
 	}
-	if (kernel_id)
-		*kernel_id = id;
+	if (kernel)
+		*kernel = g_kernels[id].name;
 	return (int)hipGetLastError();
 }
 
 extern "C" int ecg_k_launch_copy(const void *src, void *dst, uint64_t bytes, int mode, void *stream,
-				 uint32_t max_blocks, uint32_t *kernel_id)
+				 uint32_t max_blocks, const char **kernel)
 {
 	const uint64_t n16 = bytes / 16;
 	uint64_t blocks = (n16 + 4 * BLOCK - 1) / (4 * BLOCK);
@@ -507,13 +467,14 @@ extern "C" int ecg_k_launch_copy(const void *src, void *dst, uint64_t bytes, int
 	else
 		hipLaunchKernelGGL(ecg_stream_kernel<0>, dim3((uint32_t)blocks), dim3(BLOCK), 0, st,
 				   (const uint8_t *)src, (uint8_t *)dst, n16);
-	if (kernel_id)
-		*kernel_id = mode == 1 ? KID_READ : mode == 2 ? KID_WRITE : KID_COPY;
+	if (kernel)
+		*kernel = mode == 1 ? "ecg_stream_kernel<read>" : mode == 2 ? "ecg_stream_kernel<write>" :
+					"ecg_stream_kernel<copy>";
 	return (int)hipGetLastError();
 }
 
 extern "C" int ecg_k_launch_matmul_sel(const ecg_mm_params_t *p, const uint8_t *sel_dev, uint32_t ncols,
-				      void *stream, uint32_t *kernel_id)
+				      void *stream, const char **kernel)
 {
 	uint32_t gx, gy;
 
@@ -524,17 +485,17 @@ extern "C" int ecg_k_launch_matmul_sel(const ecg_mm_params_t *p, const uint8_t *
 		return (int)hipErrorInvalidValue;
 	mm_grid(p, nullptr, &gx, &gy);
 	// the DAOS classes' p = 1, 2 specialised; 3..8 parity rows runtime-shaped
-	const uint32_t v = p->rows == 1 ? 0 : p->rows == 2 ? 1 : 2;
-	if (v == 0)
+	if (p->rows == 1)
 		hipLaunchKernelGGL(ecg_mm_sel_kernel<1>, dim3(gx, gy), dim3(BLOCK), 0, (hipStream_t)stream, *p,
 				   sel_dev, ncols);
-	else if (v == 1)
+	else if (p->rows == 2)
 		hipLaunchKernelGGL(ecg_mm_sel_kernel<2>, dim3(gx, gy), dim3(BLOCK), 0, (hipStream_t)stream, *p,
 				   sel_dev, ncols);
 	else
 		hipLaunchKernelGGL(ecg_mm_sel_kernel<0>, dim3(gx, gy), dim3(BLOCK), 0, (hipStream_t)stream, *p,
 				   sel_dev, ncols);
-	if (kernel_id)
-		*kernel_id = KID_SEL + v;
+	if (kernel)
+		*kernel = p->rows == 1 ? "ecg_mm_sel_kernel<1>" : p->rows == 2 ? "ecg_mm_sel_kernel<2>" :
+					 "ecg_mm_sel_kernel<0>";
 	return (int)hipGetLastError();
 }

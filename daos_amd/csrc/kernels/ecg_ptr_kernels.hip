@@ -338,11 +338,9 @@ static const uentry g_ukernels[] = {
 	UE(1, 16), UE(2, 16), UE(3, 16), UE(0, 16), UE(1, 4), UE(2, 4), UE(3, 4), UE(0, 4),
 };
 #define N_UKERNELS ((uint32_t)(sizeof(g_ukernels) / sizeof(g_ukernels[0])))
-#define KID_UPD (ECG_KID_PTR + 60u)		/* below the byte kernels' ids */
-#define KID_UPD_BYTE (KID_UPD + N_UKERNELS)
 
 extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t *items_dev, uint32_t ncols,
-				       int granule, void *stream, uint32_t *kernel_id)
+				       int granule, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
 	const uint64_t C = p->cell_bytes;
@@ -357,8 +355,8 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 	if (granule == 0) {
 		hipLaunchKernelGGL(ecg_upd_ptr_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p, items_dev,
 				   ncols);
-		if (kernel_id)
-			*kernel_id = KID_UPD_BYTE;
+		if (kernel)
+			*kernel = "ecg_upd_ptr_byte_kernel";
 		return (int)hipGetLastError();
 	}
 	if (granule != 16 && granule != 4)
@@ -368,8 +366,8 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 			id = i;
 	mm_grid(p, nullptr, &gx, &gy);
 	hipLaunchKernelGGL(g_ukernels[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, items_dev, ncols);
-	if (kernel_id)
-		*kernel_id = KID_UPD + id;
+	if (kernel)
+		*kernel = g_ukernels[id].name;
 	return (int)hipGetLastError();
 }
 
@@ -394,24 +392,9 @@ static const pentry g_pkernels[] = {
 	PEG(8, 1, 2), PEG(8, 2, 2), PEG(8, 3, 2),	/* k = 8 inputs off 16 B (ecg_ptrs.c ptr_granule) */
 };
 #define N_PKERNELS ((uint32_t)(sizeof(g_pkernels) / sizeof(g_pkernels[0])))
-#define KID_PTR ECG_KID_PTR		/* pointer-table kernel ids: KID_PTR + index */
-#define KID_PTR_BYTE (KID_PTR + N_PKERNELS)
-
-extern "C" const char *ecg_k_ptr_kernel_name(uint32_t id)
-{
-	if (id >= KID_PTR && id < KID_PTR + N_PKERNELS)
-		return g_pkernels[id - KID_PTR].name;
-	if (id == KID_PTR_BYTE)
-		return "ecg_mm_ptr_byte_kernel";
-	if (id >= KID_UPD && id < KID_UPD + N_UKERNELS)
-		return g_ukernels[id - KID_UPD].name;
-	if (id == KID_UPD_BYTE)
-		return "ecg_upd_ptr_byte_kernel";
-	return "?";
-}
 
 extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t *cells_dev, int granule,
-				       const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+				       const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
 	int g = granule;
@@ -424,8 +407,8 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 	if (g == 0 || (cfg && cfg->variant == 2)) {	/* 0: the host found operands the
 							 * device cannot serve as dwords */
 		hipLaunchKernelGGL(ecg_mm_ptr_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p, cells_dev);
-		if (kernel_id)
-			*kernel_id = KID_PTR_BYTE;
+		if (kernel)
+			*kernel = "ecg_mm_ptr_byte_kernel";
 		return (int)hipGetLastError();
 	}
 	if (g != 16 && g != 4 && g != 2 && g != 1)
@@ -449,7 +432,7 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 	// blocks per CU as the offset kernel's (ecg_set_wg_per_cu): unused dynamic LDS
 	const size_t lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_pkernels[id].k, g_pkernels[id].r);
 	hipLaunchKernelGGL(g_pkernels[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev);
-	if (kernel_id)
-		*kernel_id = KID_PTR + id;
+	if (kernel)
+		*kernel = g_pkernels[id].name;
 	return (int)hipGetLastError();
 }

@@ -298,9 +298,8 @@ ecg_recover_masks_ptr_byte_kernel(const ecg_mm_params_t P, const u32x4 *__restri
 
 // ---------------------------------------------------------------------------
 // Dispatch: one table for both layouts.  The lane instantiations (the k of
-// the DAOS EC classes; the rest runtime-shaped), then the byte kernels; an
-// entry's index is its kernel id above ECG_KID_RECOVER_MASKS (strided) or
-// ECG_KID_RECOVER_MASKS_PTRS (cell table).
+// the DAOS EC classes; the rest runtime-shaped), then the byte kernels; the
+// launcher reports an entry's name (strided) or pname (cell table).
 // ---------------------------------------------------------------------------
 typedef void (*rm_fn_t)(const ecg_mm_params_t, const u32x4 *, const uint32_t *, unsigned long long *, uint32_t,
 			uint32_t);
@@ -326,18 +325,9 @@ static const rmentry g_rm[] = {
 #define N_RM ((uint32_t)(sizeof(g_rm) / sizeof(g_rm[0])))
 #define RM_BYTE (N_RM - 1)
 
-extern "C" const char *ecg_k_recover_masks_kernel_name(uint32_t id)
-{
-	if (id >= ECG_KID_RECOVER_MASKS && id < ECG_KID_RECOVER_MASKS + N_RM)
-		return g_rm[id - ECG_KID_RECOVER_MASKS].name;
-	if (id >= ECG_KID_RECOVER_MASKS_PTRS && id < ECG_KID_RECOVER_MASKS_PTRS + N_RM)
-		return g_rm[id - ECG_KID_RECOVER_MASKS_PTRS].pname;
-	return "?";
-}
-
 extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, const uint64_t *cells_dev,
 					  const uint32_t *masks, uint64_t *result, int bytewise, int sparse,
-					  const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+					  const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
 	uint32_t gx, gy, id = RM_BYTE;
@@ -376,7 +366,7 @@ extern "C" int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *
 	else
 		hipLaunchKernelGGL(g_rm[id].pfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, (const u32x4 *)settbl, cells_dev,
 				   masks, (unsigned long long *)result, grp, nsets);
-	if (kernel_id)
-		*kernel_id = (cells_dev ? ECG_KID_RECOVER_MASKS_PTRS : ECG_KID_RECOVER_MASKS) + id;
+	if (kernel)
+		*kernel = cells_dev ? g_rm[id].pname : g_rm[id].name;
 	return (int)hipGetLastError();
 }

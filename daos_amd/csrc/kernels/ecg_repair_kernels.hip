@@ -267,8 +267,8 @@ typedef void (*repair_fn_t)(const ecg_mm_params_t, const ecg_ptbl_t *, const uin
 typedef void (*repair_pfn_t)(const ecg_mm_params_t, const ecg_ptbl_t *, const uint64_t *, const uint32_t *,
 			     unsigned long long *);
 
-// one table for both layouts: an entry's index is its kernel id above
-// ECG_KID_REPAIR (strided) or ECG_KID_REPAIR_PTRS (cell table)
+// one table for both layouts: the launcher reports an entry's name (strided)
+// or pname (cell table)
 struct rentry {
 	int k;
 	repair_fn_t fn;
@@ -279,34 +279,20 @@ struct rentry {
 #define RE(K_) {K_, ecg_repair_kernel<K_>, ecg_repair_ptr_kernel<K_>, "ecg_repair_kernel<" #K_ ">", \
 		"ecg_repair_ptr_kernel<" #K_ ">"}
 
-// the k of the DAOS EC classes; the rest runtime-shaped
-static const rentry g_repair[] = {RE(2), RE(4), RE(8), RE(16), RE(0)};
+// the k of the DAOS EC classes; the rest runtime-shaped; then the byte kernels
+static const rentry g_repair[] = {
+	RE(2), RE(4), RE(8), RE(16), RE(0),
+	{-1, ecg_repair_byte_kernel, ecg_repair_ptr_byte_kernel, "ecg_repair_byte_kernel",
+	 "ecg_repair_ptr_byte_kernel"}};
 #define N_REPAIR ((uint32_t)(sizeof(g_repair) / sizeof(g_repair[0])))
-#define KID_REPAIR_BYTE (ECG_KID_REPAIR + N_REPAIR)
-#define KID_REPAIR_PTR_BYTE (ECG_KID_REPAIR_PTRS + N_REPAIR)
-static_assert(ECG_KID_REPAIR + N_REPAIR + 1 <= ECG_KID_REPAIR_PTRS &&
-		      ECG_KID_REPAIR_PTRS + N_REPAIR + 1 <= ECG_KID_RECOVER_MASKS,
-	      "repair ids: 850 .. 855 strided, 856 .. 861 cell table");
-
-extern "C" const char *ecg_k_repair_kernel_name(uint32_t id)
-{
-	if (id >= ECG_KID_REPAIR && id < ECG_KID_REPAIR + N_REPAIR)
-		return g_repair[id - ECG_KID_REPAIR].name;
-	if (id == KID_REPAIR_BYTE)
-		return "ecg_repair_byte_kernel";
-	if (id >= ECG_KID_REPAIR_PTRS && id < ECG_KID_REPAIR_PTRS + N_REPAIR)
-		return g_repair[id - ECG_KID_REPAIR_PTRS].pname;
-	if (id == KID_REPAIR_PTR_BYTE)
-		return "ecg_repair_ptr_byte_kernel";
-	return "?";
-}
+#define REPAIR_BYTE (N_REPAIR - 1)
 
 extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *rowtbl, const uint64_t *cells_dev,
 				   const uint32_t *status, uint64_t *result, int bytewise,
-				   const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+				   const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
-	uint32_t gx, gy;
+	uint32_t gx, gy, id = REPAIR_BYTE;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0)
 		return (int)hipSuccess;
@@ -315,36 +301,23 @@ extern "C" int ecg_k_launch_repair(const ecg_mm_params_t *p, const ecg_ptbl_t *r
 		return (int)hipErrorInvalidValue;
 	rows_grid(p, 64u, ECG_REPAIR_GRID_X, cfg, &gx, &gy);
 
-	if (bytewise) {
-		if (cells_dev == nullptr)
-			hipLaunchKernelGGL(ecg_repair_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
-					   (unsigned long long *)result);
-		else
-			hipLaunchKernelGGL(ecg_repair_ptr_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl,
-					   cells_dev, status, (unsigned long long *)result);
-		if (kernel_id)
-			*kernel_id = cells_dev ? KID_REPAIR_PTR_BYTE : KID_REPAIR_BYTE;
-		return (int)hipGetLastError();
+	if (!bytewise) {
+		// the lane kernels read and write dwordx4 at the cells' own addresses;
+		// those of a cell table the host has found 16-byte aligned (the table is
+		// not read here)
+		if ((cells_dev == nullptr && !aligned16(p)) || p->cell_bytes % 16u)
+			return (int)hipErrorInvalidValue;
+		for (id = 0; id < REPAIR_BYTE - 1; id++)	// no match: <0>, the last lane entry
+			if (g_repair[id].k == (int)p->k)
+				break;
 	}
-	// the lane kernels read and write dwordx4 at the cells' own addresses;
-	// those of a cell table the host has found 16-byte aligned (the table is
-	// not read here)
-	if ((cells_dev == nullptr && !aligned16(p)) || p->cell_bytes % 16u)
-		return (int)hipErrorInvalidValue;
-
-	uint32_t id = N_REPAIR - 1;	// <0>
-	for (uint32_t i = 0; i < N_REPAIR; i++)
-		if (g_repair[i].k == (int)p->k) {
-			id = i;
-			break;
-		}
 	if (cells_dev == nullptr)
 		hipLaunchKernelGGL(g_repair[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, status,
 				   (unsigned long long *)result);
 	else
 		hipLaunchKernelGGL(g_repair[id].pfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, rowtbl, cells_dev, status,
 				   (unsigned long long *)result);
-	if (kernel_id)
-		*kernel_id = (cells_dev ? ECG_KID_REPAIR_PTRS : ECG_KID_REPAIR) + id;
+	if (kernel)
+		*kernel = cells_dev ? g_repair[id].pname : g_repair[id].name;
 	return (int)hipGetLastError();
 }

@@ -309,8 +309,8 @@ ecg_update_masks_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *__rest
 
 // ---------------------------------------------------------------------------
 // Dispatch: one table for both layouts.  The lane instantiations, then the
-// byte kernels; an entry's index is its kernel id above ECG_KID_UPDATE_MASKS
-// (strided) or ECG_KID_UPDATE_MASKS_PTRS (cell table).
+// byte kernels; the launcher reports an entry's name (strided) or pname (cell
+// table).
 // ---------------------------------------------------------------------------
 typedef void (*um_fn_t)(const ecg_mm_params_t, const uint32_t *, unsigned long long *, uint32_t, uint32_t);
 typedef void (*ump_fn_t)(const ecg_mm_params_t, const uint64_t *, const uint32_t *, unsigned long long *, uint32_t);
@@ -332,22 +332,10 @@ static const umentry g_um[] = {UME(1), UME(2), UME(3), UME(0),
 				"ecg_update_masks_byte_kernel", "ecg_update_masks_ptr_byte_kernel"}};
 #define N_UM ((uint32_t)(sizeof(g_um) / sizeof(g_um[0])))
 #define UM_BYTE (N_UM - 1)
-static_assert(ECG_KID_UPDATE_MASKS + N_UM <= ECG_KID_UPDATE_MASKS_PTRS &&
-		      ECG_KID_UPDATE_MASKS_PTRS + N_UM <= ECG_KID_COPY_SEGS,
-	      "update_masks ids: 890 .. 894 strided, 895 .. 899 cell table");
-
-extern "C" const char *ecg_k_update_masks_kernel_name(uint32_t id)
-{
-	if (id >= ECG_KID_UPDATE_MASKS && id < ECG_KID_UPDATE_MASKS + N_UM)
-		return g_um[id - ECG_KID_UPDATE_MASKS].name;
-	if (id >= ECG_KID_UPDATE_MASKS_PTRS && id < ECG_KID_UPDATE_MASKS_PTRS + N_UM)
-		return g_um[id - ECG_KID_UPDATE_MASKS_PTRS].pname;
-	return "?";
-}
 
 extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
 					 uint64_t *result, int packed, int bytewise, int sparse,
-					 const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+					 const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
 	uint32_t gx, gy, id = UM_BYTE;
@@ -392,7 +380,7 @@ extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_
 	else
 		hipLaunchKernelGGL(g_um[id].pfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, cells_dev, masks,
 				   (unsigned long long *)result, grp);
-	if (kernel_id)
-		*kernel_id = (cells_dev ? ECG_KID_UPDATE_MASKS_PTRS : ECG_KID_UPDATE_MASKS) + id;
+	if (kernel)
+		*kernel = cells_dev ? g_um[id].pname : g_um[id].name;
 	return (int)hipGetLastError();
 }

@@ -405,8 +405,8 @@ ecg_verify_summary_kernel(const uint32_t *__restrict__ status, uint32_t nstripes
 typedef void (*verify_fn_t)(const ecg_mm_params_t, uint32_t *);
 typedef void (*verify_pfn_t)(const ecg_mm_params_t, const uint64_t *, uint32_t *);
 
-// one table for both layouts: an entry's index is its kernel id above
-// ECG_KID_VERIFY (strided) or ECG_KID_VERIFY_PTRS (cell table)
+// one table for both layouts: the launcher reports an entry's name (strided)
+// or pname (cell table)
 struct ventry {
 	int k, r;
 	verify_fn_t fn;
@@ -418,40 +418,25 @@ struct ventry {
 	{K_, R_, ecg_verify_kernel<K_, R_>, ecg_verify_ptr_kernel<K_, R_>, "ecg_verify_kernel<" #K_ "," #R_ ">",       \
 	 "ecg_verify_ptr_kernel<" #K_ "," #R_ ">"}
 
-// every (k, p) of the DAOS EC classes, as the product's; the rest runtime-shaped
+// every (k, p) of the DAOS EC classes, as the product's; the rest runtime-shaped;
+// then the byte kernels
 static const ventry g_verify[] = {
 	VE(2, 1), VE(2, 2), VE(2, 3),
 	VE(4, 1), VE(4, 2), VE(4, 3),
 	VE(8, 1), VE(8, 2), VE(8, 3),
 	VE(16, 1), VE(16, 2), VE(16, 3),
 	VE(0, 0),
-};
+	{-1, -1, ecg_verify_byte_kernel, ecg_verify_ptr_byte_kernel, "ecg_verify_byte_kernel",
+	 "ecg_verify_ptr_byte_kernel"}};
 #define N_VERIFY ((uint32_t)(sizeof(g_verify) / sizeof(g_verify[0])))
-#define KID_VERIFY_BYTE (ECG_KID_VERIFY + N_VERIFY)
-#define KID_VERIFY_SUMMARY (ECG_KID_VERIFY + N_VERIFY + 1)
-#define KID_VERIFY_PTR_BYTE (ECG_KID_VERIFY_PTRS + N_VERIFY)
-static_assert(ECG_KID_VERIFY_PTRS + N_VERIFY + 1 <= ECG_KID_REPAIR, "cell-table verify ids: 836 .. 849");
-
-extern "C" const char *ecg_k_verify_kernel_name(uint32_t id)
-{
-	if (id >= ECG_KID_VERIFY && id < ECG_KID_VERIFY + N_VERIFY)
-		return g_verify[id - ECG_KID_VERIFY].name;
-	if (id == KID_VERIFY_BYTE)
-		return "ecg_verify_byte_kernel";
-	if (id == KID_VERIFY_SUMMARY)
-		return "ecg_verify_summary_kernel";
-	if (id >= ECG_KID_VERIFY_PTRS && id < ECG_KID_VERIFY_PTRS + N_VERIFY)
-		return g_verify[id - ECG_KID_VERIFY_PTRS].pname;
-	if (id == KID_VERIFY_PTR_BYTE)
-		return "ecg_verify_ptr_byte_kernel";
-	return "?";
-}
+#define VERIFY_BYTE (N_VERIFY - 1)
 
 extern "C" int ecg_k_launch_verify(const ecg_mm_params_t *p, const uint64_t *cells_dev, uint32_t *status,
-				   int bytewise, const ecg_launch_cfg_t *cfg, void *stream, uint32_t *kernel_id)
+				   int bytewise, const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
-	uint32_t gx, gy;
+	uint32_t gx, gy, id = VERIFY_BYTE;
+	size_t lds = 0;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
 		return (int)hipSuccess;
@@ -459,35 +444,22 @@ extern "C" int ecg_k_launch_verify(const ecg_mm_params_t *p, const uint64_t *cel
 		return (int)hipErrorInvalidValue;
 	mm_grid(p, cfg, &gx, &gy);
 
-	if (bytewise) {
-		if (cells_dev == nullptr)
-			hipLaunchKernelGGL(ecg_verify_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, status);
-		else
-			hipLaunchKernelGGL(ecg_verify_ptr_byte_kernel, dim3(gx, gy), dim3(BLOCK), 0, st, *p, cells_dev,
-					   status);
-		if (kernel_id)
-			*kernel_id = cells_dev ? KID_VERIFY_PTR_BYTE : KID_VERIFY_BYTE;
-		return (int)hipGetLastError();
+	if (!bytewise) {
+		// the lane kernels read dwordx4 at the cells' own addresses; those of a
+		// cell table the host has found 16-byte aligned (the table is not read here)
+		if ((cells_dev == nullptr && !aligned16(p)) || p->cell_bytes % 16u)
+			return (int)hipErrorInvalidValue;
+		for (id = 0; id < VERIFY_BYTE - 1; id++)	// no match: <0,0>, the last lane entry
+			if (g_verify[id].k == (int)p->k && g_verify[id].r == (int)p->rows)
+				break;
+		lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_verify[id].k, g_verify[id].r);
 	}
-	// the lane kernels read dwordx4 at the cells' own addresses; those of a
-	// cell table the host has found 16-byte aligned (the table is not read here)
-	if ((cells_dev == nullptr && !aligned16(p)) || p->cell_bytes % 16u)
-		return (int)hipErrorInvalidValue;
-
-	uint32_t id = N_VERIFY - 1;	// <0,0>
-	for (uint32_t i = 0; i < N_VERIFY; i++)
-		if (g_verify[i].k == (int)p->k && g_verify[i].r == (int)p->rows) {
-			id = i;
-			break;
-		}
-	const size_t lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_verify[id].k, g_verify[id].r);
-
 	if (cells_dev == nullptr)
 		hipLaunchKernelGGL(g_verify[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, status);
 	else
 		hipLaunchKernelGGL(g_verify[id].pfn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev, status);
-	if (kernel_id)
-		*kernel_id = (cells_dev ? ECG_KID_VERIFY_PTRS : ECG_KID_VERIFY) + id;
+	if (kernel)
+		*kernel = cells_dev ? g_verify[id].pname : g_verify[id].name;
 	return (int)hipGetLastError();
 }
 

@@ -214,3 +214,24 @@ def test_stats_struct_matches_binding(ecglib):
     fields = [f.strip() for line in body.split(";") if "uint64_t" in line
               for f in line.split("uint64_t", 1)[1].split(",")]
     assert tuple(fields) == ecglib.STATS_FIELDS
+
+
+def test_launchers_report_kernel_names_not_ids():
+    """The kernel ABI hands the launched kernel's name back: no numbered kernel id, id macro or
+    id-to-name function is left anywhere under daos_amd/csrc, and every ecg_k_launch_* prototype
+    ends in `const char **kernel` -- but the two that report nothing (the summary pass rides on its
+    verify launch's name, the table fetch is no kernel a caller asked for)."""
+    csrc = os.path.join(ROOT, "daos_amd", "csrc")
+    gone = re.compile(r"ECG_KID_\w+|\bKID_\w+|kernel_id|ecg_k_\w*kernel_name")
+    for dp, _, fs in os.walk(csrc):
+        for f in fs:
+            if f.endswith((".c", ".h", ".hip")):
+                left = gone.findall(open(os.path.join(dp, f)).read())
+                assert not left, (f, sorted(set(left)))
+    kabi = re.sub(r"/\*.*?\*/", "", open(os.path.join(csrc, "ecg_kabi.h")).read(), flags=re.S)
+    protos = dict(re.findall(r"\bint (ecg_k_launch_\w+)\(([^;]*?)\);", kabi, flags=re.S))
+    silent = {"ecg_k_launch_verify_summary", "ecg_k_launch_fetch"}
+    assert len(protos) == 18 and silent < set(protos)
+    for name, args in protos.items():
+        last = " ".join(args.split(",")[-1].split())
+        assert (last == "const char **kernel") == (name not in silent), (name, last)

@@ -1037,3 +1037,30 @@ def test_singv_encode(ctx, oracle, ecglib, oc, size, route):
     for r in range(p):
         libc.free(C.cast(pbufs[r], C.c_void_p))
     assert np.array_equal(got, oracle.singv_encode(k, p, value))
+
+
+def test_stream_kernels_move_their_bytes_and_report_their_names(ecglib, ctx):
+    """ecg_dev_copy_kernel, the HBM rate probes: 257 16-byte words (one block; thread 0 takes the
+    tail word) copied, read (dst gets each thread's XOR) and written (word i = {i, 1, 2, 3}), with
+    nothing stored past what each mode writes."""
+    n = 257 * 16
+    src = rand(n, 31)
+    words = src.view(np.uint32).reshape(-1, 4)
+    folded = words[:256].copy()
+    folded[0] ^= words[256]
+    s, d = ctx.to_device(src), ctx.alloc(n + 64)
+    try:
+        for mode, name, want in (
+                (0, "ecg_stream_kernel<copy>", words),
+                (1, "ecg_stream_kernel<read>", folded),
+                (2, "ecg_stream_kernel<write>", np.array([[i, 1, 2, 3] for i in range(257)], dtype=np.uint32))):
+            d.fill(0xEE)
+            ctx.copy_kernel(d.ptr, s.ptr, n, mode)
+            ctx.sync()
+            assert ecglib.last_kernel() == name
+            got = d.download()
+            assert np.array_equal(got[:want.nbytes].view(np.uint32).reshape(-1, 4), want), name
+            assert (got[want.nbytes:] == 0xEE).all(), name
+    finally:
+        s.free()
+        d.free()

@@ -14,8 +14,9 @@ def rand(shape, seed):
 
 @pytest.mark.parametrize("order", [0, 1, 2, 3])
 @pytest.mark.parametrize("S,C_", [(24, 8192), (13, 5000), (7, 4096 * 3 + 16)])
-def test_orders_encode_and_update(ctx, oracle, order, S, C_):
+def test_orders_encode_and_update(ctx, oracle, ecglib, order, S, C_):
     k, p = 8, 2
+    exact = C_ % 16 == 0                      # 16-byte lanes: the shape's own instantiations
     data = rand((S, k, C_), S * 7 + C_)
     en = oracle.cauchy1(k, p)
     want = np.stack([oracle.encode_data(en[k:], data[s]) for s in range(S)], axis=1)   # [p][S][C]
@@ -27,12 +28,16 @@ def test_orders_encode_and_update(ctx, oracle, order, S, C_):
         ctx.sync()
         got = par.download().reshape(p, S, C_)
         assert np.array_equal(got, want)
+        name = ecglib.last_kernel()
+        assert name == "ecg_mm_kernel<8,2,0,0>" if exact else name.startswith("ecg_mm_kernel<"), (order, name)
         # accumulate: replace cell 3 of every stripe (old ^ new), parity in place
         new = rand((S, 1, C_), 99)
         nd = ctx.to_device(new)
         old3 = ctx.to_device(np.ascontiguousarray(data[:, 3:4]))
         ctx.update(k, p, C_, S, [3], old3.ptr, nd.ptr, C_, par.ptr, S * C_, C_)
         ctx.sync()
+        name = ecglib.last_kernel()
+        assert name == "ecg_mm_kernel<1,2,1,1>" if exact else name.startswith("ecg_mm_kernel<"), (order, name)
         d2 = data.copy()
         d2[:, 3] = new[:, 0]
         want2 = np.stack([oracle.encode_data(en[k:], d2[s]) for s in range(S)], axis=1)

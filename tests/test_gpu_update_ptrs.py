@@ -86,9 +86,9 @@ def test_update_ptrs_matches_oracle(ctx, oracle, ecglib, k, p, C_, align):
         if C_ % 4:
             assert kname == "ecg_upd_ptr_byte_kernel", kname
         elif align == 16 and C_ % 16 == 0:
-            assert kname.startswith("ecg_upd_ptr_kernel<") and kname.endswith(",g16>"), kname
+            assert kname == f"ecg_upd_ptr_kernel<{p if p <= 3 else 0},g16>", kname
         else:
-            assert kname.endswith(",g4>"), kname
+            assert kname == f"ecg_upd_ptr_kernel<{p if p <= 3 else 0},g4>", kname
         # the untouched old/new cells are unchanged
         for i in range(nreq):
             assert np.array_equal(got[(npar + i) * slot + off:(npar + i) * slot + off + C_], olds[i])

@@ -36,13 +36,6 @@ def test_prototype_has_10_arguments():
     assert len(dict((s[0], s) for s in ecg._SIGS)[NAME][2]) == 10
 
 
-def test_kernel_ids_sit_between_the_strided_ones_and_the_segment_copy():
-    kabi = open(os.path.join(ROOT, "daos_amd", "csrc", "ecg_kabi.h")).read()
-    ids = {m.group(1): int(m.group(2)) for m in re.finditer(r"#define (ECG_KID_\w+) (\d+)u?\b", kabi)}
-    assert ids["ECG_KID_UPDATE_MASKS"] == 890 and ids["ECG_KID_UPDATE_MASKS_PTRS"] == 895
-    assert ids["ECG_KID_UPDATE_MASKS_PTRS"] + 5 <= ids["ECG_KID_COPY_SEGS"]
-
-
 def call(ctx=None, k=K, p=P, C__=C_, S__=S_, masks=MASKS, result=RESULT, flags=0):
     n = S_ * (2 * k + p)
     cells = (C.c_void_p * n)(*[0x10000000 + i * 2 * C_ for i in range(n)])
