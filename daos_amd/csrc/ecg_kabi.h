@@ -510,6 +510,49 @@ static inline ECG_KABI_HD int ecg_update_mask_read(uint32_t mask, int k)
 }
 
 /*
+ * ecg_csum_updated: the checksums of the parity cells ecg_update_masks rewrote
+ * (kernels/ecg_csum_kernels.hip cs_updated).  A wave takes one (stripe s, parity
+ * row r, chunk c) of the S x p x nch items and skips it unless
+ * ecg_update_mask_read(masks[s], k) > 0, so a clean stripe costs its items one
+ * mask load each.  Row r of stripe s lies at src + r*cell_stride +
+ * s*stripe_stride (either may be negative); chunk c of a cell is [c*chunk_bytes,
+ * min((c+1)*chunk_bytes, C)); its checksum goes to index s*csum_stripe_stride +
+ * r*csum_cell_stride + c of out (slots of the checksum's length at any byte).
+ * The item (s, 0, 0) counts its stripe into result (NULL: not counted):
+ * result[0] += stripes read as 1 .. k cells, result[1] = min(result[1], lowest
+ * stripe with a bit at or above k), result[2] += p per stripe of word 0,
+ * result[3] += stripes with such a bit.
+ * cells_dev == NULL: the strided parity above.  Otherwise
+ * ecg_csum_updated_ptrs: the table of ecg_update_masks_ptrs, parity row r of
+ * stripe s at the address cells_dev[s * (2k + p) + 2k + r] (device memory, read
+ * only for the launch; src and the parity strides unused); an item loads its
+ * entry after the mask test, so a skipped item reads none and no item reads an
+ * old or new data entry.  bytewise is then the host's lane choice, 0 only when
+ * EVERY parity entry, cell_bytes and chunk_bytes are multiples of 16: the
+ * launcher does not read the table.
+ * Its launcher, ecg_k_launch_csum_updated (kernels/ecg_csum_kernels.hip), is
+ * declared in host/ecg_internal.h beside the host code that calls it.
+ */
+typedef struct ecg_csum_updated_params {
+	const uint8_t *src;
+	uint8_t *out;
+	const void *tbl;
+	const uint32_t *masks;
+	uint64_t *result;
+	const uint64_t *cells_dev;
+	int64_t cell_stride, stripe_stride;
+	uint64_t csum_stripe_stride, csum_cell_stride;
+	uint64_t cell_bytes;
+	uint64_t chunk_bytes;
+	uint64_t init, xorout, poly;
+	uint32_t nstripes;
+	uint32_t nch;
+	uint32_t k, p;
+	uint32_t type;
+	uint32_t bytewise;
+} ecg_csum_updated_params_t;
+
+/*
  * The set table of one (k, p), device memory, built by host/
  * ecg_recover_masks.c: entry i (the set of index i) is ECG_RM_ENT_Q(k, p)
  * 16-byte words,

@@ -1193,6 +1193,361 @@ int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32
 	return ecg_staged_close(ctx, &t, st, rc);
 }
 
+/*
+ * ecg_csum_updated and its kin: the checksums of the parity cells a masked
+ * update rewrote, the step after ecg_update_masks / ecg_update_masks_ptrs
+ * (ecg_update_masks.c), whose mask reading, parity addressing, table and
+ * three-group test these calls share.
+ */
+
+/* The geometry of an ecg_csum_updated call once its arguments passed */
+struct updated_geom {
+	uint64_t rcs;		/* record chunk bytes */
+	uint64_t span;		/* bytes from csums to the end of the farthest slot */
+	uint32_t nch;
+};
+
+/* Do the S x p ranges of nch checksums at index s*ss + r*cs lie apart?  The two
+ * orderings that can be proven: rows inside a stripe's range, or stripes inside
+ * a row's.  A stride whose count is 1 is not looked at. */
+static int updated_strides_ok(uint64_t nch, int p, uint32_t S, uint64_t ss, uint64_t cs)
+{
+	const int rows = p > 1, stripes = S > 1;
+	uint64_t in;
+	int a, b;
+
+	a = (!rows || cs >= nch) &&
+	    (!stripes || (!__builtin_mul_overflow(rows ? cs : 0, (uint64_t)(p - 1), &in) &&
+			  !__builtin_add_overflow(in, nch, &in) && ss >= in));
+	b = (!stripes || ss >= nch) &&
+	    (!rows || (!__builtin_mul_overflow(stripes ? ss : 0, (uint64_t)(S - 1), &in) &&
+		       !__builtin_add_overflow(in, nch, &in) && cs >= in));
+	return a || b;
+}
+
+/* Argument checks of ecg_csum_updated in their documented order, everything but
+ * the context; result == NULL is accepted with need_result = 0 (a composite's
+ * checksum launch counts nothing, and passes its update half's result so that
+ * csums is held clear of it).  table: the checks of a cell-table call that come
+ * before its context check -- no parity; what csums must not overlap there is
+ * checked entry by entry later. */
+static int updated_check(const char *fn, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
+			 uint32_t S, int table, const void *parity, int64_t parity_cell_stride,
+			 int64_t parity_stripe_stride, const uint32_t *masks, const void *csums, uint64_t css, uint64_t ccs,
+			 const void *result, int need_result, unsigned flags, struct updated_geom *g)
+{
+	const int cl = ecg_csum_len(type);
+	const uint64_t rcs = ecg_csum_record_chunksize(chunksize, rec_size);
+	uint64_t nch, n, a, b;
+
+	memset(g, 0, sizeof(*g));
+	if (cl < 0)
+		return ecg_fail(-ECG_DER_NOTSUPPORTED, "%s: hash type %d not supported", fn, type);
+	if (k < 1 || k > ECG_KMAX_K || p < 1 || p > ECG_KMAX_R)
+		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
+				ECG_KMAX_K, ECG_KMAX_R);
+	if (flags & ECG_UM_PACKED)
+		return ecg_fail(-ECG_DER_INVAL, "%s: ECG_UM_PACKED has no meaning here (it packs the data images, "
+				"not the parity)", fn);
+	if (flags & ~ECG_RM_SPARSE)
+		return ecg_fail(-ECG_DER_INVAL, "%s: unknown flags 0x%x", fn, flags);
+	if (rcs == 0)
+		return ecg_fail(-ECG_DER_INVAL, "%s: chunksize and rec_size must not be 0", fn);
+	if (C % rec_size)
+		return ecg_fail(-ECG_DER_INVAL, "%s: cell_bytes %llu is not a multiple of rec_size %llu", fn,
+				(unsigned long long)C, (unsigned long long)rec_size);
+	nch = C / rcs + (C % rcs != 0);
+	/* the kernel's item count S * p * nch and every slot's byte offset fit 64 bits */
+	if (nch > UINT32_MAX || __builtin_mul_overflow(nch * (uint64_t)p, (uint64_t)cl * S, &n))
+		return ecg_fail(-ECG_DER_INVAL, "%s: too many checksums", fn);
+	if (S && C) {
+		if (__builtin_mul_overflow(S > 1 ? css : 0, (uint64_t)(S - 1), &a) ||
+		    __builtin_mul_overflow(p > 1 ? ccs : 0, (uint64_t)(p - 1), &b) || __builtin_add_overflow(a, b, &a) ||
+		    __builtin_add_overflow(a, nch, &a) || __builtin_mul_overflow(a, (uint64_t)cl, &g->span))
+			return ecg_fail(-ECG_DER_INVAL, "%s: too many checksums", fn);
+		if (!updated_strides_ok(nch, p, S, css, ccs))
+			return ecg_fail(-ECG_DER_INVAL, "%s: csum strides %llu (stripe) and %llu (cell) do not keep "
+					"the %u x %d ranges of %llu checksums apart", fn, (unsigned long long)css,
+					(unsigned long long)ccs, S, p, (unsigned long long)nch);
+	}
+	g->rcs = rcs;
+	g->nch = (uint32_t)nch;
+	if (masks == NULL || (uintptr_t)masks % 4u)
+		return ecg_fail(-ECG_DER_INVAL, "%s: masks must be 4-byte aligned device memory", fn);
+	if ((need_result && result == NULL) || (uintptr_t)result % 8u)
+		return ecg_fail(-ECG_DER_INVAL, "%s: result must be 8-byte aligned device memory", fn);
+	if (S == 0 || C == 0)
+		return 0;
+	if (!table && parity == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL parity", fn);
+	if (csums == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL csums", fn);
+	/* the span ecg_update_masks holds its masks and result clear of */
+	if (!table &&
+	    ecg_cells_overlap(csums, g->span, parity, S, parity_stripe_stride, p, parity_cell_stride, C))
+		return ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the parity", fn);
+	if (ranges_overlap(csums, g->span, masks, 4ull * S))
+		return ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the masks", fn);
+	if (result != NULL && ranges_overlap(csums, g->span, result, 32))
+		return ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the result", fn);
+	return 0;
+}
+
+/* The table checks of the two cell-table calls, made on the caller's table before
+ * the context is used (ecg_staged_open then only copies it): no NULL table, no
+ * NULL entry, and no `clear` range inside a cell from column `from` of a row on
+ * -- 2k: the parity cells, all that ecg_csum_updated_ptrs reads; 0: every cell.
+ * The message names the entry. */
+static int updated_table_check(const char *fn, void *const *cells, int k, int p, uint64_t C, uint32_t S,
+			       uint32_t from, const struct ecg_clear *clear, int nclear)
+{
+	const uint32_t n = (uint32_t)(2 * k + p);
+
+	if (S == 0 || C == 0)
+		return 0;
+	if (cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL cells", fn);
+	for (uint64_t s = 0; s < S; s++)
+		for (uint32_t c = 0; c < n; c++) {
+			const size_t i = (size_t)(s * n + c);
+
+			if (cells[i] == NULL)
+				return ecg_fail(-ECG_DER_INVAL, "%s: NULL cell %zu", fn, i);
+			for (int r = 0; c >= from && r < nclear; r++)
+				if (ranges_overlap(clear[r].at, clear[r].len, cells[i], C))
+					return ecg_fail(-ECG_DER_INVAL, "%s: %s overlaps cell %zu", fn, clear[r].what, i);
+		}
+	return 0;
+}
+
+/* One ecg_csum_updated launch on st; result NULL = nothing counted.  Over the
+ * strided parity, or with cells_dev over a staged update table (bytewise: a
+ * parity entry, C or the chunk size is no multiple of 16). */
+static int updated_launch(ecg_ctx_t *ctx, int type, const void *tbl, const struct updated_geom *g, int k, int p,
+			  uint64_t C, uint32_t S, const void *parity, int64_t parity_cell_stride,
+			  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
+			  void *csums, uint64_t css, uint64_t ccs, void *result, hipStream_t st)
+{
+	ecg_csum_updated_params_t prm;
+	const char *kernel = NULL;
+	int e;
+
+	memset(&prm, 0, sizeof(prm));
+	HASH_FILL(&prm, type, tbl);
+	prm.src = parity;
+	prm.out = csums;
+	prm.masks = masks;
+	prm.result = result;
+	prm.cells_dev = cells_dev;
+	prm.bytewise = (uint32_t)bytewise;
+	prm.cell_stride = parity_cell_stride;
+	prm.stripe_stride = parity_stripe_stride;
+	prm.csum_stripe_stride = css;
+	prm.csum_cell_stride = ccs;
+	prm.cell_bytes = C;
+	prm.chunk_bytes = g->rcs;
+	prm.nstripes = S;
+	prm.nch = g->nch;
+	prm.k = (uint32_t)k;
+	prm.p = (uint32_t)p;
+	prm.type = (uint32_t)type;
+	ecg_trace_push(cells_dev ? "ecg:csum_updated_ptrs" : "ecg:csum_updated");
+	e = ecg_k_launch_csum_updated(&prm, (void *)st, ctx->csum_blocks, &kernel);
+	return ecg_launch_done(ctx, e, cells_dev ? "csum_updated_ptrs kernel launch" : "csum_updated kernel launch", 1,
+			       kernel);
+}
+
+/* ECG_RM_SPARSE is accepted and ignored, as in ecg_csum_masked: the one grid
+ * serves dense and clean batches alike. */
+int ecg_csum_updated(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
+		     uint32_t S, const void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		     const uint32_t *masks, void *csums, uint64_t css, uint64_t ccs, void *result, unsigned flags,
+		     void *stream)
+{
+	struct updated_geom g;
+	const void *tbl;
+	hipStream_t st;
+	int rc;
+
+	rc = updated_check("csum_updated", type, chunksize, rec_size, k, p, C, S, 0, parity, parity_cell_stride,
+			   parity_stripe_stride, masks, csums, css, ccs, result, 1, flags, &g);
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "csum_updated: NULL context");
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	/* result = {0, UINT64_MAX, 0, 0}, as ecg_update_masks presets it */
+	rc = ecg_result_reset(result, st, "csum_updated memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
+	rc = hash_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	return updated_launch(ctx, type, tbl, &g, k, p, C, S, parity, parity_cell_stride, parity_stripe_stride, NULL, 0,
+			      masks, csums, css, ccs, result, st);
+}
+
+int ecg_csum_updated_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size, int k, int p, uint64_t C,
+			  uint32_t S, void *const *cells, const uint32_t *masks, void *csums, uint64_t css,
+			  uint64_t ccs, void *result, unsigned flags, void *stream)
+{
+	static const char fn[] = "csum_updated_ptrs";
+	struct ecg_staged t;
+	struct updated_geom g;
+	const void *tbl;
+	int64_t pc, ps;
+	uint64_t bits;
+	hipStream_t st;
+	int rc;
+
+	rc = updated_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, 0, masks, csums, css, ccs, result, 1,
+			   flags, &g);
+	if (rc == 0) {
+		/* held clear of the parity cells only: the old and new data cells
+		 * are not read */
+		const struct ecg_clear clear[3] = {
+			{csums, g.span, "csums"}, {masks, 4ull * S, "masks"}, {result, 32, "result"}};
+
+		rc = updated_table_check(fn, cells, k, p, C, S, 2u * (uint32_t)k, clear, 3);
+	}
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* result = {0, UINT64_MAX, 0, 0} and nothing else */
+		return ecg_result_reset(result, st, "csum_updated_ptrs memset");
+	rc = hash_tbl(ctx, type, &tbl);
+	if (rc == 0)
+		rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(2 * k + p), C, NULL, 0, &t);
+	if (rc)
+		return rc;
+	/* ecg_csum_updated's own layout, and csums clear of the whole parity span
+	 * as it demands: its launch, with no table */
+	if (ecg_um_parity_group(t.sc->pin, k, p, C, S, &pc, &ps, &bits) &&
+	    !ecg_cells_overlap(csums, g.span, cells[2 * k], S, ps, p, pc, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_csum_updated(ctx, type, chunksize, rec_size, k, p, C, S, cells[2 * k], pc, ps, masks, csums,
+					css, ccs, result, flags, stream);
+	}
+	rc = ecg_staged_upload(&t, result, st, "csum_updated_ptrs memset", "csum_updated_ptrs cell table");
+	if (rc == 0)
+		rc = updated_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, 0, t.sc->dev, (bits | C | g.rcs) % 16u != 0,
+				    masks, csums, css, ccs, result, st);
+	return ecg_staged_close(ctx, &t, st, rc);
+}
+
+/* Both halves' argument errors, but the NULL context, before anything is queued:
+ * the update's (ecg_um_check), then updated_check.  ECG_UM_PACKED concerns the
+ * update half alone. */
+int ecg_update_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
+			  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
+			  int64_t parity_stripe_stride, const uint32_t *masks, void *result, unsigned flags, int type,
+			  uint64_t chunksize, uint64_t rec_size, void *csums, uint64_t css, uint64_t ccs, void *stream)
+{
+	static const char fn[] = "update_masks_csum";
+	struct updated_geom g;
+	const void *tbl;
+	int rc;
+
+	rc = ecg_um_check(fn, 1, 1, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride, parity_stripe_stride,
+			  NULL, masks, result, flags);
+	if (rc == 0)
+		rc = updated_check(fn, type, chunksize, rec_size, k, p, C, S, 0, parity, parity_cell_stride,
+				   parity_stripe_stride, masks, csums, css, ccs, result, 0, flags & ~ECG_UM_PACKED, &g);
+	/* csums clear of every old and new cell the update half may read (packed
+	 * or not, they lie within k cells of a stripe's start) */
+	if (rc == 0 && S && C && ecg_cells_overlap(csums, g.span, old_cells, S, upd_stripe_stride, k, (int64_t)C, C))
+		rc = ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the old cells", fn);
+	if (rc == 0 && S && C && ecg_cells_overlap(csums, g.span, new_cells, S, upd_stripe_stride, k, (int64_t)C, C))
+		rc = ecg_fail(-ECG_DER_INVAL, "%s: csums overlaps the new cells", fn);
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	rc = ecg_update_masks(ctx, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity, parity_cell_stride,
+			      parity_stripe_stride, masks, result, flags, stream);
+	if (rc || S == 0 || C == 0)
+		return rc;
+	rc = hash_tbl(ctx, type, &tbl);
+	if (rc)
+		return rc;
+	return updated_launch(ctx, type, tbl, &g, k, p, C, S, parity, parity_cell_stride, parity_stripe_stride, NULL, 0,
+			      masks, csums, css, ccs, NULL, ecg_pick_stream(ctx, stream));
+}
+
+int ecg_update_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+			       const uint32_t *masks, void *result, unsigned flags, int type, uint64_t chunksize,
+			       uint64_t rec_size, void *csums, uint64_t css, uint64_t ccs, void *stream)
+{
+	static const char fn[] = "update_masks_ptrs_csum";
+	struct ecg_staged t;
+	struct updated_geom g;
+	const void *tbl;
+	int64_t us, pc, ps;
+	uint64_t bits;
+	hipStream_t st;
+	int rc;
+
+	/* (no stripes, so no table yet: updated_table_check looks at it once both
+	 * halves' other arguments passed) */
+	rc = ecg_um_check(fn, 0, 1, k, p, C, 0, NULL, NULL, NULL, 0, 0, NULL, masks, result, flags);
+	if (rc == 0)
+		rc = updated_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, 0, masks, csums, css, ccs, result,
+				   0, flags, &g);
+	if (rc == 0) {
+		/* csums clear of every cell the update half may read, too */
+		const struct ecg_clear clear[3] = {
+			{masks, 4ull * S, "masks"}, {result, 32, "result"}, {csums, g.span, "csums"}};
+
+		rc = updated_table_check(fn, cells, k, p, C, S, 0, clear, 3);
+	}
+	if (rc)
+		return rc;
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "%s: NULL context", fn);
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing updated, nothing checksummed */
+		return ecg_result_reset(result, st, "update_masks_ptrs_csum memset");
+	rc = hash_tbl(ctx, type, &tbl);
+	/* the table was checked above and is staged once for the two launches */
+	if (rc == 0)
+		rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(2 * k + p), C, NULL, 0, &t);
+	if (rc)
+		return rc;
+	/* the layout of ecg_update_masks_csum, and masks, result and csums clear of
+	 * the spans it demands: that call, with no table */
+	if (ecg_um_three_groups(t.sc->pin, k, p, C, S, &us, &pc, &ps) &&
+	    !ecg_cells_overlap(masks, 4ull * S, cells[2 * k], S, ps, p, pc, C) &&
+	    !ecg_cells_overlap(result, 32, cells[2 * k], S, ps, p, pc, C) &&
+	    !ecg_cells_overlap(csums, g.span, cells[2 * k], S, ps, p, pc, C) &&
+	    !ecg_cells_overlap(csums, g.span, cells[0], S, us, k, (int64_t)C, C) &&
+	    !ecg_cells_overlap(csums, g.span, cells[k], S, us, k, (int64_t)C, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_update_masks_csum(ctx, k, p, C, S, cells[0], cells[k], us, cells[2 * k], pc, ps, masks, result,
+					     flags, type, chunksize, rec_size, csums, css, ccs, stream);
+	}
+	(void)ecg_um_parity_group(t.sc->pin, k, p, C, S, &pc, &ps, &bits);
+	rc = ecg_staged_upload(&t, result, st, "update_masks_ptrs_csum memset", "update_masks_ptrs_csum cell table");
+	if (rc == 0)
+		rc = ecg_um_launch(ctx, fn, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks,
+				   result, flags, st);
+	if (rc == 0)
+		rc = updated_launch(ctx, type, tbl, &g, k, p, C, S, NULL, 0, 0, t.sc->dev, (bits | C | g.rcs) % 16u != 0,
+				    masks, csums, css, ccs, NULL, st);
+	/* the fetch and both kernels read the slot */
+	return ecg_staged_close(ctx, &t, st, rc);
+}
+
 /* Fused product + checksum parameters (ecg_kabi.h) for output cells of C
  * bytes that start on chunk boundaries.  Returns 1 when the fused kernels
  * can take the request, 0 when the caller must run the product and

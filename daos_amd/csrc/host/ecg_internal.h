@@ -222,6 +222,31 @@ int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int
 		  void *stripes, int64_t stripe_stride, const uint64_t *cells_dev, int bytewise,
 		  const uint32_t *masks, void *result, unsigned flags, hipStream_t st);
 
+/* what ecg_update_masks, ecg_update_masks_ptrs and, in ecg_csum.c, their _csum
+ * composites and ecg_csum_updated_ptrs share (ecg_update_masks.c) */
+/* the argument checks of the update calls in their documented order (fn: the
+ * caller's name in the message; have_ctx = 0 fails where they report a NULL
+ * context).  strided = 1: ecg_update_masks's operands; 0: the table form
+ * (`cells`; its entries are checked by ecg_staged_open), which has no packed
+ * form */
+int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
+		 const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
+		 int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
+		 unsigned flags);
+/* the update launch over the three strided images, or with cells_dev over a
+ * staged table of S x (2k + p) entries; fn names the call */
+int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
+		  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
+		  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
+		  void *result, unsigned flags, hipStream_t st);
+/* is the parity group of tab[S][2k + p] strided (p0 + s*ps + r*pc)?  *bits: the
+ * OR of the parity addresses */
+int ecg_um_parity_group(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *pc, int64_t *ps,
+			uint64_t *bits);
+/* is tab[S][2k + p] three strided groups (old and new with one stride us)? */
+int ecg_um_three_groups(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *us, int64_t *pc,
+			int64_t *ps);
+
 /* what the strided and the cell-table scrub calls share (ecg_verify.c):
  * ecg_verify, ecg_repair, ecg_verify_ptrs, ecg_repair_ptrs, ecg_scrub_ptrs */
 /* zeroed launch parameters with the shape (k, rows = p, C, S) and, with
@@ -245,6 +270,13 @@ int ecg_scrub_ptrs_check(const char *fn, int have_ctx, int k, int p, uint64_t C,
 
 /* checksums (ecg_csum.c) */
 void ecg_csum_ctx_fini(ecg_ctx_t *ctx);
+/* The launcher of ecg_csum_updated and, with p->cells_dev, ecg_csum_updated_ptrs
+ * (kernels/ecg_csum_kernels.hip, extern "C"; the parameters are ecg_kabi.h's);
+ * max_blocks 0 = default.  *kernel: ecg_crc_updated_kernel<type> /
+ * ecg_adler_updated_kernel, their ecg_*_updated_ptr_kernel counterparts over a
+ * table, <..bytes> when the chunks do not all start and end 16-byte aligned. */
+int ecg_k_launch_csum_updated(const ecg_csum_updated_params_t *p, void *stream, uint32_t max_blocks,
+			      const char **kernel);
 int ecg_csum_fused_params(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
 			  uint64_t C, int k, int rows, void *csums, int src, ecg_mmcs_params_t *q);
 

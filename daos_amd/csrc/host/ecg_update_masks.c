@@ -22,7 +22,8 @@
  * (ecg_internal.h ecg_staged_open / _upload / _close), and the cell-table
  * kernels of the same file.  A table that is three strided images after all
  * is handed to ecg_update_masks.  The two calls share the argument check, the
- * launch helper and its ecg_launch_done.
+ * launch helper and its ecg_launch_done; so do their _csum composites and
+ * ecg_csum_updated_ptrs (ecg_csum.c), through ecg_internal.h.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -34,10 +35,10 @@
  * strided = 1: ecg_update_masks, whose operands are checked before the
  * context; 0: ecg_update_masks_ptrs, whose table is checked after it (`cells`;
  * its entries by ecg_staged_open) and which has no packed form. */
-static int um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
-		    const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
-		    int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
-		    unsigned flags)
+int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
+		 const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
+		 int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
+		 unsigned flags)
 {
 	if (k < 1 || k > ECG_KMAX_K || p < 1 || p > ECG_KMAX_R)
 		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
@@ -76,10 +77,10 @@ static int um_check(const char *fn, int strided, int have_ctx, int k, int p, uin
 /* The launch of both calls (fn names the call in the trace range and the
  * messages): over the three strided images, or with cells_dev over the staged
  * cell table (the strided operands unused). */
-static int um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
-		     const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
-		     int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
-		     void *result, unsigned flags, hipStream_t st)
+int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
+		  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
+		  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
+		  void *result, unsigned flags, hipStream_t st)
 {
 	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
 	const int ptrs = cells_dev != NULL;
@@ -132,7 +133,7 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	hipStream_t st;
 	int rc;
 
-	rc = um_check(fn, 1, ctx != NULL, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride,
+	rc = ecg_um_check(fn, 1, ctx != NULL, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride,
 		      parity_stripe_stride, NULL, masks, result, flags);
 	if (rc)
 		return rc;
@@ -145,26 +146,52 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	rc = ecg_result_reset(result, st, "update_masks memset");
 	if (rc || S == 0 || C == 0)
 		return rc;
-	return um_launch(ctx, fn, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity, parity_cell_stride,
+	return ecg_um_launch(ctx, fn, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity, parity_cell_stride,
 			 parity_stripe_stride, NULL,
 			 ((uintptr_t)old_cells | (uintptr_t)new_cells | (uintptr_t)parity | (uint64_t)upd_stripe_stride |
 			  (uint64_t)parity_cell_stride | (uint64_t)parity_stripe_stride | C) % 16u != 0,
 			 masks, result, flags, st);
 }
 
+/* Is the parity group of the staged table tab[S][2k + p] strided -- parity
+ * (s, r) at p0 + s*ps + r*pc?  *bits = the OR of the parity addresses (the lane
+ * choice of a call that reads no other entry).  The strides are differences of
+ * addresses and may be negative. */
+int ecg_um_parity_group(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *pc, int64_t *ps,
+			uint64_t *bits)
+{
+	const uint32_t n = (uint32_t)(2 * k + p);
+	const uint64_t p0 = tab[2 * k];
+	const uint64_t c = p > 1 ? tab[2 * k + 1] - p0 : C;
+	const uint64_t q = S > 1 ? tab[n + 2 * k] - p0 : C;
+	uint64_t all = 0;
+	int aff = 1;
+
+	for (uint64_t s = 0; s < S; s++)
+		for (int r = 0; r < p; r++) {
+			const uint64_t a = tab[s * n + 2 * (uint64_t)k + r];
+
+			aff &= a == p0 + s * q + (uint64_t)r * c;
+			all |= a;
+		}
+	*pc = (int64_t)c;
+	*ps = (int64_t)q;
+	*bits = all;
+	return aff;
+}
+
 /* Is the staged table tab[S][2k + p] three strided groups -- old cell (s, j)
  * at o0 + s*us + j*C, new cell (s, j) at n0 + s*us + j*C with the same us,
  * parity (s, r) at p0 + s*ps + r*pc?  One stripe is, when its cells are spaced
  * so.  The strides are differences of addresses and may be negative. */
-static int um_three_groups(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *us, int64_t *pc,
-			   int64_t *ps)
+int ecg_um_three_groups(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *us, int64_t *pc,
+			int64_t *ps)
 {
 	const uint32_t n = (uint32_t)(2 * k + p);
-	const uint64_t o0 = tab[0], n0 = tab[k], p0 = tab[2 * k];
+	const uint64_t o0 = tab[0], n0 = tab[k];
 	const uint64_t u = S > 1 ? tab[n] - o0 : (uint64_t)k * C;
-	const uint64_t c = p > 1 ? tab[2 * k + 1] - p0 : C;
-	const uint64_t q = S > 1 ? tab[n + 2 * k] - p0 : C;
-	int aff = 1;
+	uint64_t bits;
+	int aff = ecg_um_parity_group(tab, k, p, C, S, pc, ps, &bits);
 
 	for (uint64_t s = 0; s < S; s++) {
 		const uint64_t *row = tab + s * n;
@@ -173,12 +200,8 @@ static int um_three_groups(const uint64_t *tab, int k, int p, uint64_t C, uint32
 			aff &= row[j] == o0 + s * u + (uint64_t)j * C;
 			aff &= row[k + j] == n0 + s * u + (uint64_t)j * C;
 		}
-		for (int r = 0; r < p; r++)
-			aff &= row[2 * k + r] == p0 + s * q + (uint64_t)r * c;
 	}
 	*us = (int64_t)u;
-	*pc = (int64_t)c;
-	*ps = (int64_t)q;
 	return aff;
 }
 
@@ -194,7 +217,7 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	hipStream_t st;
 	int rc;
 
-	rc = um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags);
+	rc = ecg_um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags);
 	if (rc)
 		return rc;
 	rc = ecg_ctx_enter(ctx);
@@ -210,7 +233,7 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	/* ecg_update_masks's own layout (and masks and result clear of the whole
 	 * parity span, gaps included, as it demands): its launch, with no table
 	 * and no dependent address loads */
-	if (um_three_groups(t.sc->pin, k, p, C, S, &us, &pc, &ps) &&
+	if (ecg_um_three_groups(t.sc->pin, k, p, C, S, &us, &pc, &ps) &&
 	    !ecg_cells_overlap(masks, 4ull * S, cells[2 * k], S, ps, p, pc, C) &&
 	    !ecg_cells_overlap(result, 32, cells[2 * k], S, ps, p, pc, C)) {
 		ecg_staged_close(ctx, &t, st, 0);
@@ -219,7 +242,7 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	}
 	rc = ecg_staged_upload(&t, result, st, "update_masks_ptrs memset", "update_masks_ptrs cell table");
 	if (rc == 0)
-		rc = um_launch(ctx, fn, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks,
+		rc = ecg_um_launch(ctx, fn, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks,
 			       result, flags, st);
 	return ecg_staged_close(ctx, &t, st, rc);
 }

@@ -27,8 +27,8 @@
 //
 // Each kernel family is built from one body.  The wave-per-item kernels of
 // extents, of masked cells and of cell tables are crc_wave / adler_wave over an
-// addressing struct (cs_extents, cs_masked<PTRS>, cs_cells); the group and split
-// kernels keep their own
+// addressing struct (cs_extents, cs_masked<PTRS>, cs_updated<PTRS>, cs_cells); the
+// group and split kernels keep their own
 // loops and take the CRC prologue and finish (crc_lane) and the adler32 sums
 // (adler_lane, adler_wave_sum, adler_finish) from the same helpers.
 #include <hip/hip_runtime.h>
@@ -369,6 +369,82 @@ struct cs_masked {
 	}
 };
 
+// ecg_csum_updated: the checksums of the parity cells ecg_update_masks rewrote
+// (ecg_kabi.h ecg_csum_updated_params_t), a wave per (stripe, parity row, chunk).
+// Item g = (s * p + r) * nch + c reads masks[s] (wave-uniform) and is skipped
+// unless ecg_update_mask_read reads the word as 1 .. k cells -- the one reading
+// the update kernels make of it -- so a clean stripe costs its items one load
+// each; the item (s, 0, 0) counts its stripe into result.  No address derives
+// from the mask's bits, only from s, r < p and c < nch: all 2^32 mask values are
+// safe.
+// PTRS (ecg_csum_updated_ptrs): the cell's address is the entry s * (2k + p) +
+// 2k + r of the table p.cells_dev -- one wave-uniform 8-byte load per item, after
+// the mask test, so a skipped item reads no entry and no item ever reads an old
+// or a new data entry.
+template <bool PTRS>
+struct cs_updated {
+	using params = ecg_csum_updated_params_t;
+
+	static __device__ __forceinline__ uint64_t total(const params &p)
+	{
+		return (uint64_t)p.nstripes * p.p * p.nch;
+	}
+	static __device__ __forceinline__ uint32_t wave() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+	static __device__ __forceinline__ bool item(const params &p, uint64_t g, const uint8_t *&base, uint64_t &len,
+						    uint64_t &slot)
+	{
+		const uint64_t per = (uint64_t)p.p * p.nch;
+		uint64_t s;
+		uint32_t r, c;
+
+		if (((g | per) >> 32) == 0) {	// as chunk_geom_fast: 32-bit divisions when the counts allow
+			const uint32_t s32 = (uint32_t)g / (uint32_t)per, rem = (uint32_t)g - s32 * (uint32_t)per;
+
+			s = s32;
+			r = rem / p.nch;
+			c = rem - r * p.nch;
+		} else {
+			const uint64_t rem = g % per;
+
+			s = g / per;
+			r = (uint32_t)(rem / p.nch);
+			c = (uint32_t)(rem - (uint64_t)r * p.nch);
+		}
+		const uint32_t m = p.masks[s];
+		const int rd = ecg_update_mask_read(m, (int)p.k);
+
+		if (r == 0 && c == 0 && m != 0 && p.result != nullptr && (threadIdx.x & 63) == 0) {
+			unsigned long long *res = (unsigned long long *)p.result;
+
+			if (rd > 0) {
+				atomicAdd(&res[0], 1ull);
+				atomicAdd(&res[2], (unsigned long long)p.p);
+			} else {
+				atomicMin(&res[1], (unsigned long long)s);
+				atomicAdd(&res[3], 1ull);
+			}
+		}
+		if (rd <= 0)
+			return false;
+		const uint64_t off = (uint64_t)c * p.chunk_bytes;	// < cell_bytes: c < nch
+
+		len = p.cell_bytes - off < p.chunk_bytes ? p.cell_bytes - off : p.chunk_bytes;
+		if constexpr (PTRS)
+			// (r comes from a scalar g: uniform, and said so for the scalar load)
+			base = table_cell(p.cells_dev,
+					  s * (2 * p.k + p.p) + __builtin_amdgcn_readfirstlane(2 * p.k + r)) + off;
+		else
+			base = p.src + (int64_t)s * p.stripe_stride + (int64_t)r * p.cell_stride + off;
+		slot = s * p.csum_stripe_stride + r * p.csum_cell_stride + c;
+		return true;
+	}
+	template <int LEN, typename T>
+	static __device__ __forceinline__ void store(const params &p, uint64_t slot, T v)
+	{
+		store_at<LEN>(p.out + slot * LEN, v);
+	}
+};
+
 // ecg_csum_cells_ptrs: every chunk of every cell of a table, item g = chunk
 // g % nch of the cell at cells_dev[g / nch] (a wave-uniform load); the checksums
 // are an array indexed by g that may lie at any byte.
@@ -469,6 +545,18 @@ template <int W, bool REFL, bool ALIGNED, int TK>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_crc_masked_ptr_kernel(ecg_csum_masked_params_t p)
 {
 	crc_wave<W, REFL, ALIGNED, TK, cs_masked<true>>(p);
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_updated_kernel(ecg_csum_updated_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_updated<false>>(p);
+}
+
+template <int W, bool REFL, bool ALIGNED, int TK>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_crc_updated_ptr_kernel(ecg_csum_updated_params_t p)
+{
+	crc_wave<W, REFL, ALIGNED, TK, cs_updated<true>>(p);
 }
 
 template <int W, bool REFL, bool ALIGNED, int TK>
@@ -726,6 +814,18 @@ __global__ __launch_bounds__(CS_BLOCK) void ecg_adler_masked_ptr_kernel(ecg_csum
 }
 
 template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_updated_kernel(ecg_csum_updated_params_t p)
+{
+	adler_wave<ALIGNED, cs_updated<false>>(p);
+}
+
+template <bool ALIGNED>
+__global__ __launch_bounds__(CS_BLOCK) void ecg_adler_updated_ptr_kernel(ecg_csum_updated_params_t p)
+{
+	adler_wave<ALIGNED, cs_updated<true>>(p);
+}
+
+template <bool ALIGNED>
 __global__ __launch_bounds__(CS_BLOCK) void ecg_adler_cells_ptr_kernel(ecg_csum_masked_params_t p)
 {
 	adler_wave<ALIGNED, cs_cells>(p);
@@ -897,6 +997,29 @@ const csum_entry<ecg_csum_masked_params_t> g_masked_ptr[] = {
 	{7, false, ecg_adler_masked_ptr_kernel<false>, "ecg_adler_masked_ptr_kernel<bytes>"},
 };
 
+// ecg_csum_updated and ecg_csum_updated_ptrs
+const csum_entry<ecg_csum_updated_params_t> g_updated[] = {
+	{1, true, ecg_crc_updated_kernel<16, false, true, TK_4>, "ecg_crc_updated_kernel<crc16>"},
+	{1, false, ecg_crc_updated_kernel<16, false, false, TK_5>, "ecg_crc_updated_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_updated_kernel<32, true, true, TK_4>, "ecg_crc_updated_kernel<crc32>"},
+	{2, false, ecg_crc_updated_kernel<32, true, false, TK_5>, "ecg_crc_updated_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_updated_kernel<64, true, true, TK_4>, "ecg_crc_updated_kernel<crc64>"},
+	{3, false, ecg_crc_updated_kernel<64, true, false, TK_5>, "ecg_crc_updated_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_updated_kernel<true>, "ecg_adler_updated_kernel"},
+	{7, false, ecg_adler_updated_kernel<false>, "ecg_adler_updated_kernel<bytes>"},
+};
+
+const csum_entry<ecg_csum_updated_params_t> g_updated_ptr[] = {
+	{1, true, ecg_crc_updated_ptr_kernel<16, false, true, TK_4>, "ecg_crc_updated_ptr_kernel<crc16>"},
+	{1, false, ecg_crc_updated_ptr_kernel<16, false, false, TK_5>, "ecg_crc_updated_ptr_kernel<crc16,bytes>"},
+	{2, true, ecg_crc_updated_ptr_kernel<32, true, true, TK_4>, "ecg_crc_updated_ptr_kernel<crc32>"},
+	{2, false, ecg_crc_updated_ptr_kernel<32, true, false, TK_5>, "ecg_crc_updated_ptr_kernel<crc32,bytes>"},
+	{3, true, ecg_crc_updated_ptr_kernel<64, true, true, TK_4>, "ecg_crc_updated_ptr_kernel<crc64>"},
+	{3, false, ecg_crc_updated_ptr_kernel<64, true, false, TK_5>, "ecg_crc_updated_ptr_kernel<crc64,bytes>"},
+	{7, true, ecg_adler_updated_ptr_kernel<true>, "ecg_adler_updated_ptr_kernel"},
+	{7, false, ecg_adler_updated_ptr_kernel<false>, "ecg_adler_updated_ptr_kernel<bytes>"},
+};
+
 const csum_entry<ecg_csum_masked_params_t> g_cells_ptr[] = {
 	{1, true, ecg_crc_cells_ptr_kernel<16, false, true, TK_4>, "ecg_crc_cells_ptr_kernel<crc16>"},
 	{1, false, ecg_crc_cells_ptr_kernel<16, false, false, TK_5>, "ecg_crc_cells_ptr_kernel<crc16,bytes>"},
@@ -951,6 +1074,33 @@ extern "C" int ecg_k_launch_csum_masked(const ecg_csum_masked_params_t *p, void 
 		return launch_row(g_masked_ptr, aligned, (total + CS_WAVES - 1) / CS_WAVES,
 				  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel);
 	return launch_row(g_masked, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks ? max_blocks : 256 * 16,
+			  CS_BLOCK, p, stream, kernel);
+}
+
+extern "C" int ecg_k_launch_csum_updated(const ecg_csum_updated_params_t *p, void *stream, uint32_t max_blocks,
+					 const char **kernel)
+{
+	const uint64_t total = (uint64_t)p->nstripes * p->p * p->nch;
+	const bool ptrs = p->cells_dev != nullptr;
+	// as ecg_k_launch_csum_masked: every chunk starts 16-byte aligned only when
+	// the base, both parity strides and the two sizes are; of a cell table the
+	// host says so, and the sizes must agree
+	const bool aligned = ptrs ? !p->bytewise
+				  : (((uint64_t)(uintptr_t)p->src | (uint64_t)p->cell_stride |
+				      (uint64_t)p->stripe_stride | p->cell_bytes | p->chunk_bytes) & 15u) == 0;
+
+	if (total == 0)
+		return (int)hipSuccess;
+	if (p->k == 0 || p->k > ECG_KMAX_K || p->p == 0 || p->p > ECG_KMAX_R || p->masks == nullptr ||
+	    p->out == nullptr || (!ptrs && p->src == nullptr) || p->chunk_bytes == 0 ||
+	    (uint64_t)(p->nch - 1) * p->chunk_bytes >= p->cell_bytes ||
+	    (ptrs && aligned && ((p->cell_bytes | p->chunk_bytes) & 15u)))
+		return (int)hipErrorInvalidValue;
+	// as ecg_k_launch_csum: 16 blocks per CU, grid-stride beyond
+	if (ptrs)
+		return launch_row(g_updated_ptr, aligned, (total + CS_WAVES - 1) / CS_WAVES,
+				  max_blocks ? max_blocks : 256 * 16, CS_BLOCK, p, stream, kernel);
+	return launch_row(g_updated, aligned, (total + CS_WAVES - 1) / CS_WAVES, max_blocks ? max_blocks : 256 * 16,
 			  CS_BLOCK, p, stream, kernel);
 }
 

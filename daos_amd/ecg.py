@@ -221,6 +221,17 @@ _SIGS = [
                                       vp, vp]),
     ("ecg_recover_masks_ptrs_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
                                               C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp, vp, vp]),
+    ("ecg_csum_updated", C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp,
+                                   C.c_int64, C.c_int64, vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint, vp]),
+    ("ecg_csum_updated_ptrs", C.c_int, [vp, C.c_int, C.c_uint64, C.c_uint64, C.c_int, C.c_int, C.c_uint64,
+                                        C.c_uint32, C.POINTER(vp), vp, vp, C.c_uint64, C.c_uint64, vp, C.c_uint,
+                                        vp]),
+    ("ecg_update_masks_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, C.c_int64, vp,
+                                        C.c_int64, C.c_int64, vp, vp, C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp,
+                                        C.c_uint64, C.c_uint64, vp]),
+    ("ecg_update_masks_ptrs_csum", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
+                                             C.c_uint, C.c_int, C.c_uint64, C.c_uint64, vp, C.c_uint64, C.c_uint64,
+                                             vp]),
     ("ecg_set_csum_all_route", C.c_int, [vp, C.c_uint32]),
 ]
 
@@ -818,6 +829,49 @@ class Context:
         _chk(lib().ecg_recover_masks_ptrs_csum(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks,
                                                result, flags, htype, chunksize, rec_size, csums, src_csums,
                                                stream), "recover_masks_ptrs_csum")
+
+    def csum_updated(self, htype: int, chunksize: int, rec_size: int, k: int, p: int, cell_bytes: int,
+                     nstripes: int, parity: int, parity_cell_stride: int, parity_stripe_stride: int, masks: int,
+                     csums: int, csum_stripe_stride: int, csum_cell_stride: int, result: int, flags: int = 0,
+                     stream=None):
+        """ecg_csum_updated: checksum the p parity cells of every stripe whose device word masks[s]
+        update_masks() reads as 1..k changed cells -- the parity it rewrote -- chunk c of row r of
+        stripe s into checksum index s*csum_stripe_stride + r*csum_cell_stride + c of csums
+        (strides in checksums).  Parity addressed as in update_masks(); result: device memory for
+        four uint64 (stripes checksummed, lowest stripe with an invalid mask, parity cells
+        checksummed, stripes with an invalid mask)."""
+        _chk(lib().ecg_csum_updated(self.h, htype, chunksize, rec_size, k, p, cell_bytes, nstripes, parity,
+                                    parity_cell_stride, parity_stripe_stride, masks, csums, csum_stripe_stride,
+                                    csum_cell_stride, result, flags, stream), "csum_updated")
+
+    def csum_updated_ptrs(self, htype: int, chunksize: int, rec_size: int, k: int, p: int, cell_bytes: int,
+                          nstripes: int, cells: Sequence[int] | None, masks: int, csums: int,
+                          csum_stripe_stride: int, csum_cell_stride: int, result: int, flags: int = 0, stream=None):
+        """ecg_csum_updated_ptrs: csum_updated() over the table update_masks_ptrs() takes, parity
+        cell r of stripe s = cells[s*(2k+p) + 2k + r]; the old and new data cells are not read."""
+        _chk(lib().ecg_csum_updated_ptrs(self.h, htype, chunksize, rec_size, k, p, cell_bytes, nstripes,
+                                         self._cell_table(cells), masks, csums, csum_stripe_stride, csum_cell_stride,
+                                         result, flags, stream), "csum_updated_ptrs")
+
+    def update_masks_csum(self, k: int, p: int, cell_bytes: int, nstripes: int, old: int, new: int,
+                          upd_stripe_stride: int, parity: int, parity_cell_stride: int, parity_stripe_stride: int,
+                          masks: int, result: int, htype: int, chunksize: int, rec_size: int, csums: int,
+                          csum_stripe_stride: int, csum_cell_stride: int, flags: int = 0, stream=None):
+        """ecg_update_masks_csum: update_masks(), then csum_updated() into csums, on one stream.
+        result: update_masks()'s; flags: RM_SPARSE, UM_PACKED (the update half's)."""
+        _chk(lib().ecg_update_masks_csum(self.h, k, p, cell_bytes, nstripes, old, new, upd_stripe_stride, parity,
+                                         parity_cell_stride, parity_stripe_stride, masks, result, flags, htype,
+                                         chunksize, rec_size, csums, csum_stripe_stride, csum_cell_stride, stream),
+             "update_masks_csum")
+
+    def update_masks_ptrs_csum(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None,
+                               masks: int, result: int, htype: int, chunksize: int, rec_size: int, csums: int,
+                               csum_stripe_stride: int, csum_cell_stride: int, flags: int = 0, stream=None):
+        """ecg_update_masks_ptrs_csum: update_masks_csum() over a table of cell addresses; the table
+        is staged once for the update and the checksum launch."""
+        _chk(lib().ecg_update_masks_ptrs_csum(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks,
+                                              result, flags, htype, chunksize, rec_size, csums, csum_stripe_stride,
+                                              csum_cell_stride, stream), "update_masks_ptrs_csum")
 
     def set_csum_all_route(self, route: int = 0):
         """Source checksums of *_csum_all: 0 measured default, 1 fused kernel, 2 two passes."""

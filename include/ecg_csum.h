@@ -262,6 +262,134 @@ int ecg_recover_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_byte
 				int type, uint64_t chunksize, uint64_t rec_size,
 				void *csums, void *src_csums, void *stream);
 
+/* Checksum the parity cells ecg_update_masks (ecg.h) REWROTE, and no others:
+ * the step after a masked update, as ecg_csum_masked is the step after
+ * ecg_recover_masks.  The rewritten parity cells are stored with chunk
+ * checksums like any other extent; the masks stay on the device, and a sparse
+ * batch costs the checksums of the handful of stripes that changed instead of
+ * ecg_csum_extents over all nstripes * p parity cells.
+ * The parity is addressed exactly as in ecg_update_masks: row r of stripe s at
+ * parity + r*parity_cell_stride + s*parity_stripe_stride -- the client layout
+ * [p][S][C] (a padded pitch included) and the recovery layout with parity =
+ * stripes + k*C alike; either stride may be negative.  parity and masks are read
+ * only.  With m = masks[s], read as ecg_update_masks reads it:
+ *   m == 0                    nothing of the stripe is read, no slot is written;
+ *                             it is not counted
+ *   a bit at or above k set   nothing is read or written; the stripe is counted
+ *                             in result[3] and result[1]
+ *   otherwise (1..k bits)     all p parity cells of the stripe are checksummed
+ * All 2^32 mask values are safe.  Each selected cell is taken as an extent from
+ * record index 0, as ecg_csum_masked takes its cells: nch = ecg_csum_chunk_count(
+ * chunksize, rec_size, 0, cell_bytes / rec_size) checksums of ecg_csum_len(type)
+ * bytes, little-endian.  Chunk c of row r of stripe s goes to checksum index
+ * s*csum_stripe_stride + r*csum_cell_stride + c of csums (strides in checksums,
+ * not bytes, as in ecg_csum_mask; csums at any byte): [p][S][nch], what
+ * ecg_encode_csum writes, is cell stride S*nch and stripe stride nch; the parity
+ * columns of an [S][k+p][nch] array are csums advanced by k*nch checksums,
+ * stripe stride (k+p)*nch, cell stride nch, where an ecg_csum_mask over that
+ * array sees the new parity checksums.  No byte outside the selected cells'
+ * slots is written.  The nstripes * p ranges of nch slots must lie apart, in one
+ * of the two orders that can be proven: cell_stride >= nch and stripe_stride >=
+ * (p-1)*cell_stride + nch, or stripe_stride >= nch and cell_stride >=
+ * (nstripes-1)*stripe_stride + nch; a stride whose count is 1 (p == 1,
+ * nstripes == 1) is not looked at.
+ * result: device memory, four uint64 (8-byte aligned): stripes checksummed,
+ * lowest stripe with an invalid mask (UINT64_MAX if none), parity cells
+ * checksummed (p times word 0), stripes with an invalid mask -- words 0, 1 and
+ * 3 are what ecg_update_masks leaves for the same masks; {0, UINT64_MAX, 0, 0}
+ * and nothing else touched when nstripes or cell_bytes is 0.  INVALID MASKS ARE
+ * REPORTED THROUGH result ONLY.
+ * Limits: k <= 16, p <= 8 (ecg_update_masks's, not ecg_csum_masked's p <= 3);
+ * the four hash types.  Any alignment: parity, both parity strides, cell_bytes
+ * and the record chunk size all multiples of 16 run the 16-byte-load kernels
+ * ecg_crc_updated_kernel<type> / ecg_adler_updated_kernel, anything else their
+ * <..bytes> forms for the whole launch.  flags: ECG_RM_SPARSE is accepted and
+ * changes nothing; ECG_UM_PACKED is refused by name (it packs the data images,
+ * not the parity).  ecg_set_csum_launch caps the workgroups.  Asynchronous on
+ * `stream`.  Telemetry: `launches` counts the launch; `csum_chunks` is not
+ * advanced, the count being known on the device only (result word 2 times nch).
+ * Errors, found before the context is used, the message prefixed
+ * "csum_updated:", in this order: -ECG_DER_NOTSUPPORTED for an unknown hash
+ * type; then -ECG_DER_INVAL for k or p beyond the limits; ECG_UM_PACKED, an
+ * unknown flag; chunksize or rec_size 0; cell_bytes % rec_size != 0; too many
+ * checksums (nstripes * p * nch checksums, or the farthest slot's byte offset,
+ * beyond 64 bits) and the stride rule above (both only with nstripes and
+ * cell_bytes non-zero); masks NULL or not 4-byte aligned; result NULL or not
+ * 8-byte aligned (both also for nstripes == 0); and, nstripes and cell_bytes
+ * non-zero: parity NULL; csums NULL; csums sharing a byte with the parity's byte
+ * span, gaps included (the span ecg_update_masks holds its masks and result
+ * clear of); csums overlapping the masks; csums overlapping the result.  Last, a
+ * NULL context. */
+int ecg_csum_updated(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
+		     int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		     const void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		     const uint32_t *masks, void *csums, uint64_t csum_stripe_stride,
+		     uint64_t csum_cell_stride, void *result, unsigned flags, void *stream);
+
+/* ecg_csum_updated over the TABLE OF ecg_update_masks_ptrs (ecg.h): cells, a HOST
+ * array of nstripes * (2k+p) device addresses, the parity cell r of stripe s
+ * being entry s*(2k+p) + 2k + r -- one table serves the update and its
+ * checksums.  The table is copied before the call returns (the caller may
+ * overwrite or free it at once).  Every entry is checked for NULL, the old and
+ * new data entries included (the same table, the same rule as the update call),
+ * but the data cells are never read and may alias anything; an item loads its
+ * parity entry only after the mask test, at an index that is always 2k + r, r <
+ * p, for a word that read as 1..k bits.  Everything else is ecg_csum_updated's,
+ * word for word.
+ * Errors, all found before the context is used, in this order:
+ * ecg_csum_updated's own up to and including the result's (the message prefixed
+ * "csum_updated_ptrs:"); then, nstripes and cell_bytes non-zero: csums NULL;
+ * csums overlapping the masks or the result; cells NULL; a NULL entry (named by
+ * its index); csums, masks or result sharing a byte with a PARITY cell
+ * ("overlaps", and the entry's index).  Last, a NULL context.
+ * A table whose parity entries are p0 + s*ps + r*pc (negative strides too) and
+ * whose arguments pass ecg_csum_updated's own checks IS the call
+ * ecg_csum_updated(parity = p0, pc, ps): no table is uploaded and
+ * ecg_last_kernel names the strided kernel.  Any other table runs
+ * ecg_crc_updated_ptr_kernel<type> / ecg_adler_updated_ptr_kernel with 16-byte
+ * loads when EVERY PARITY entry, cell_bytes and the record chunk size are
+ * multiples of 16 (the data entries do not matter), and their <..bytes> forms
+ * for the WHOLE launch when one is not. */
+int ecg_csum_updated_ptrs(ecg_ctx_t *ctx, int type, uint64_t chunksize, uint64_t rec_size,
+			  int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			  void *const *cells, const uint32_t *masks, void *csums,
+			  uint64_t csum_stripe_stride, uint64_t csum_cell_stride,
+			  void *result, unsigned flags, void *stream);
+
+/* ecg_update_masks, then ecg_csum_updated into csums, on one stream: the
+ * aggregation update of a batch with one set of changed cells per stripe and
+ * the checksums of the parity it rewrote.  Two launches, not a fused kernel.
+ * result: ecg_update_masks's four words (the checksum launch counts nothing).
+ * flags: ecg_update_masks's; ECG_UM_PACKED is accepted, it affects the update
+ * half alone.  The argument errors of both halves are returned before anything
+ * is queued, the message prefixed "update_masks_csum:": ecg_update_masks's in
+ * their order, then ecg_csum_updated's, then csums sharing a byte with the span
+ * of the old or of the new image (every cell the update half may read), then a
+ * NULL context. */
+int ecg_update_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			  const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
+			  void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+			  const uint32_t *masks, void *result, unsigned flags, int type,
+			  uint64_t chunksize, uint64_t rec_size, void *csums,
+			  uint64_t csum_stripe_stride, uint64_t csum_cell_stride, void *stream);
+
+/* ecg_update_masks_csum over a table of cell addresses: ecg_update_masks_ptrs,
+ * then ecg_csum_updated_ptrs without a result, on one stream; the table is
+ * checked and staged ONCE for both launches.  result: ecg_update_masks's four
+ * words.  Errors before anything is queued: ecg_update_masks_ptrs's argument
+ * checks up to the result's (ECG_UM_PACKED refused), ecg_csum_updated_ptrs's;
+ * then cells NULL and, entry by entry, a NULL entry and masks, result or csums
+ * sharing a byte with ANY cell of the table, old and new data cells included;
+ * last, a NULL context.
+ * An affine table that passes ecg_update_masks_ptrs's shortcut, and whose
+ * checksum array is clear of the parity span and of the two image spans, is the
+ * call ecg_update_masks_csum.  The caller's contract of ecg_update_masks_ptrs
+ * (no parity cell overlaps another cell) holds here too. */
+int ecg_update_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+			       void *const *cells, const uint32_t *masks, void *result, unsigned flags,
+			       int type, uint64_t chunksize, uint64_t rec_size, void *csums,
+			       uint64_t csum_stripe_stride, uint64_t csum_cell_stride, void *stream);
+
 /* Route of the source checksums of ecg_encode_csum_all / ecg_recover_csum_all:
  * 0 the measured default per (hash type, k, output rows), 1 the fused kernel
  * wherever it can take the request, 2 always two passes.  Same results. */
