@@ -510,6 +510,29 @@ static inline ECG_KABI_HD int ecg_update_mask_read(uint32_t mask, int k)
 }
 
 /*
+ * ecg_agg_masks' reading of (mask word, k, T), shared by the host and the
+ * kernels (kernels/ecg_update_masks_kernels.hip): what a stripe gets.  NOTHING
+ * for mask 0; REFUSE for a bit at or above k (left as it is and counted); with
+ * n = 1 .. k cells named, DELTA -- ecg_update_masks's update -- for n <= T and
+ * RECALC -- the re-encode of the merged stripe -- for n > T.  T = 0 .. k (the
+ * callers check): 0 re-encodes every stripe with work, k none.
+ */
+#define ECG_AGG_REFUSE (-1)
+#define ECG_AGG_NOTHING 0
+#define ECG_AGG_DELTA 1
+#define ECG_AGG_RECALC 2
+static inline ECG_KABI_HD int ecg_agg_route(uint32_t mask, int k, uint32_t T)
+{
+	const int n = ecg_update_mask_read(mask, k);
+
+	if (n == ECG_UM_NONE)
+		return ECG_AGG_NOTHING;
+	if (n == ECG_UM_RANGE)
+		return ECG_AGG_REFUSE;
+	return (uint32_t)n > T ? ECG_AGG_RECALC : ECG_AGG_DELTA;
+}
+
+/*
  * ecg_csum_updated: the checksums of the parity cells ecg_update_masks rewrote
  * (kernels/ecg_csum_kernels.hip cs_updated).  A wave takes one (stripe s, parity
  * row r, chunk c) of the S x p x nch items and skips it unless
@@ -628,7 +651,10 @@ int ecg_k_launch_recover_masks(const ecg_mm_params_t *p, const void *settbl, con
  * EVERY table entry 16-byte aligned (the host's check: the launcher does not
  * read the table) and cell_bytes % 16 == 0.
  * *kernel: ecg_update_masks_kernel<p> / ecg_update_masks_byte_kernel, or their
- * ecg_update_masks_ptr_* counterparts over a table. */
+ * ecg_update_masks_ptr_* counterparts over a table.
+ * The launcher of ecg_agg_masks over the same operands, ecg_k_launch_agg_masks
+ * (the same file), is declared in host/ecg_internal.h beside the host code
+ * that calls it. */
 int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
 			      uint64_t *result, int packed, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
 			      void *stream, const char **kernel);

@@ -1457,7 +1457,7 @@ int ecg_update_masks_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	int rc;
 
 	rc = ecg_um_check(fn, 1, 1, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride, parity_stripe_stride,
-			  NULL, masks, result, flags);
+			  NULL, masks, result, flags, NULL);
 	if (rc == 0)
 		rc = updated_check(fn, type, chunksize, rec_size, k, p, C, S, 0, parity, parity_cell_stride,
 				   parity_stripe_stride, masks, csums, css, ccs, result, 0, flags & ~ECG_UM_PACKED, &g);
@@ -1497,7 +1497,7 @@ int ecg_update_masks_ptrs_csum(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_
 
 	/* (no stripes, so no table yet: updated_table_check looks at it once both
 	 * halves' other arguments passed) */
-	rc = ecg_um_check(fn, 0, 1, k, p, C, 0, NULL, NULL, NULL, 0, 0, NULL, masks, result, flags);
+	rc = ecg_um_check(fn, 0, 1, k, p, C, 0, NULL, NULL, NULL, 0, 0, NULL, masks, result, flags, NULL);
 	if (rc == 0)
 		rc = updated_check(fn, type, chunksize, rec_size, k, p, C, S, 1, NULL, 0, 0, masks, csums, css, ccs, result,
 				   0, flags, &g);

@@ -228,17 +228,32 @@ int ecg_rm_launch(ecg_ctx_t *ctx, const char *fn, const void *settbl, int k, int
  * caller's name in the message; have_ctx = 0 fails where they report a NULL
  * context).  strided = 1: ecg_update_masks's operands; 0: the table form
  * (`cells`; its entries are checked by ecg_staged_open), which has no packed
- * form */
+ * form.  recalc_above != NULL: the caller is ecg_agg_masks / _ptrs -- packed is
+ * refused, the threshold checked right after the flags and *recalc_above left
+ * as the effective one, 0 .. k; NULL: an update call */
 int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
 		 const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
 		 int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
-		 unsigned flags);
+		 unsigned flags, uint32_t *recalc_above);
 /* the update launch over the three strided images, or with cells_dev over a
  * staged table of S x (2k + p) entries; fn names the call */
 int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
 		  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
 		  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
 		  void *result, unsigned flags, hipStream_t st);
+/* The launcher of ecg_agg_masks and, with cells_dev, ecg_agg_masks_ptrs
+ * (kernels/ecg_update_masks_kernels.hip, extern "C"): ecg_k_launch_update_masks's
+ * operands (ecg_kabi.h; never packed), counters, lane / byte choice and grids,
+ * with the route of a stripe read by ecg_agg_route(masks[s], k, recalc_above):
+ * a DELTA stripe gets that launcher's update; a RECALC stripe gets parity[r] =
+ * XOR_{j < k} tbl[r][j] * (bit j of the mask ? new_j : old_j), its old parity
+ * unread and every data cell read from one image.  recalc_above <= k
+ * (hipErrorInvalidValue otherwise).  *kernel: ecg_agg_masks_kernel<p> /
+ * ecg_agg_masks_byte_kernel, or their ecg_agg_masks_ptr_* counterparts over a
+ * table. */
+int ecg_k_launch_agg_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+			   uint64_t *result, uint32_t recalc_above, int bytewise, int sparse,
+			   const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* is the parity group of tab[S][2k + p] strided (p0 + s*ps + r*pc)?  *bits: the
  * OR of the parity addresses */
 int ecg_um_parity_group(const uint64_t *tab, int k, int p, uint64_t C, uint32_t S, int64_t *pc, int64_t *ps,

@@ -24,6 +24,12 @@
  * is handed to ecg_update_masks.  The two calls share the argument check, the
  * launch helper and its ecg_launch_done; so do their _csum composites and
  * ecg_csum_updated_ptrs (ecg_csum.c), through ecg_internal.h.
+ *
+ * ecg_agg_masks / ecg_agg_masks_ptrs are the same two calls with a route per
+ * stripe: the delta update for a stripe that names few cells, a re-encode of
+ * the merged stripe for one that names more than `recalc_above` (ecg_kabi.h
+ * ecg_agg_route; the ecg_agg_masks* kernels of the same file).  They take the
+ * same checks, widened by the threshold, and the same launch helper.
  */
 #include <stdlib.h>
 #include <string.h>
@@ -38,7 +44,7 @@
 int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64_t C, uint32_t S,
 		 const void *old_cells, const void *new_cells, const void *parity, int64_t parity_cell_stride,
 		 int64_t parity_stripe_stride, const void *cells, const uint32_t *masks, const void *result,
-		 unsigned flags)
+		 unsigned flags, uint32_t *recalc_above)
 {
 	if (k < 1 || k > ECG_KMAX_K || p < 1 || p > ECG_KMAX_R)
 		return ecg_fail(-ECG_DER_INVAL, "%s: k=%d p=%d outside the limits k <= %d, p <= %d", fn, k, p,
@@ -48,6 +54,16 @@ int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64
 	if (!strided && (flags & ECG_UM_PACKED))
 		return ecg_fail(-ECG_DER_INVAL, "%s: ECG_UM_PACKED has no meaning over a cell table (slot j holds "
 				"the address of cell j)", fn);
+	if (recalc_above != NULL) {
+		if (flags & ECG_UM_PACKED)
+			return ecg_fail(-ECG_DER_INVAL, "%s: ECG_UM_PACKED is refused (a re-encoded stripe needs the "
+					"unnamed old cells in their slots)", fn);
+		if (*recalc_above == ECG_AGG_AUTO)
+			*recalc_above = (uint32_t)ecg_agg_threshold(k, p);
+		else if (*recalc_above > (uint32_t)k)
+			return ecg_fail(-ECG_DER_INVAL, "%s: recalc_above=%u is neither 0 .. k=%d nor ECG_AGG_AUTO", fn,
+					*recalc_above, k);
+	}
 	if (masks == NULL || (uintptr_t)masks % 4u)
 		return ecg_fail(-ECG_DER_INVAL, "%s: masks must be 4-byte aligned device memory", fn);
 	if (result == NULL || (uintptr_t)result % 8u)
@@ -74,13 +90,12 @@ int ecg_um_check(const char *fn, int strided, int have_ctx, int k, int p, uint64
 	return 0;
 }
 
-/* The launch of both calls (fn names the call in the trace range and the
- * messages): over the three strided images, or with cells_dev over the staged
- * cell table (the strided operands unused). */
-int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
-		  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
-		  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
-		  void *result, unsigned flags, hipStream_t st)
+/* The launch of all four calls: agg = 0 the update with its flags, 1
+ * ecg_agg_masks / _ptrs with the effective threshold T. */
+static int um_launch(ecg_ctx_t *ctx, const char *fn, int agg, uint32_t T, int k, int p, uint64_t C, uint32_t S,
+		     const void *old_cells, const void *new_cells, int64_t upd_stripe_stride, void *parity,
+		     int64_t parity_cell_stride, int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise,
+		     const uint32_t *masks, void *result, unsigned flags, hipStream_t st)
 {
 	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
 	const int ptrs = cells_dev != NULL;
@@ -114,14 +129,32 @@ int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint
 			ecg_build_ptbl(en[(k + r) * k + j], &prm->tbl[r][j]);
 	}
 
-	ecg_trace_push(ptrs ? "ecg:update_masks_ptrs" : "ecg:update_masks");
-	e = ecg_k_launch_update_masks(prm, cells_dev, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0,
-				      ctx->cfg.variant == 2 || bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg,
-				      (void *)st, &kernel);
+	bytewise = ctx->cfg.variant == 2 || bytewise;
+	if (agg) {
+		ecg_trace_push(ptrs ? "ecg:agg_masks_ptrs" : "ecg:agg_masks");
+		e = ecg_k_launch_agg_masks(prm, cells_dev, masks, (uint64_t *)result, T, bytewise,
+					   (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kernel);
+	} else {
+		ecg_trace_push(ptrs ? "ecg:update_masks_ptrs" : "ecg:update_masks");
+		e = ecg_k_launch_update_masks(prm, cells_dev, masks, (uint64_t *)result, (flags & ECG_UM_PACKED) != 0,
+					      bytewise, (flags & ECG_RM_SPARSE) != 0, &ctx->cfg, (void *)st, &kernel);
+	}
 	free(prm);
 	/* update_cells / update_bytes stay: the count is known on the device only */
-	return ecg_launch_done(ctx, e, ptrs ? "update_masks_ptrs kernel launch" : "update_masks kernel launch", 1,
-			       kernel);
+	return ecg_launch_done(ctx, e, agg ? (ptrs ? "agg_masks_ptrs kernel launch" : "agg_masks kernel launch") :
+			       (ptrs ? "update_masks_ptrs kernel launch" : "update_masks kernel launch"), 1, kernel);
+}
+
+/* The launch of the update calls (fn names the call in the trace range and
+ * the messages): over the three strided images, or with cells_dev over the
+ * staged cell table (the strided operands unused). */
+int ecg_um_launch(ecg_ctx_t *ctx, const char *fn, int k, int p, uint64_t C, uint32_t S, const void *old_cells,
+		  const void *new_cells, int64_t upd_stripe_stride, void *parity, int64_t parity_cell_stride,
+		  int64_t parity_stripe_stride, const uint64_t *cells_dev, int bytewise, const uint32_t *masks,
+		  void *result, unsigned flags, hipStream_t st)
+{
+	return um_launch(ctx, fn, 0, 0, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity, parity_cell_stride,
+			 parity_stripe_stride, cells_dev, bytewise, masks, result, flags, st);
 }
 
 int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
@@ -134,7 +167,7 @@ int ecg_update_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
 	int rc;
 
 	rc = ecg_um_check(fn, 1, ctx != NULL, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride,
-		      parity_stripe_stride, NULL, masks, result, flags);
+		      parity_stripe_stride, NULL, masks, result, flags, NULL);
 	if (rc)
 		return rc;
 	rc = ecg_ctx_enter(ctx);
@@ -217,7 +250,7 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	hipStream_t st;
 	int rc;
 
-	rc = ecg_um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags);
+	rc = ecg_um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags, NULL);
 	if (rc)
 		return rc;
 	rc = ecg_ctx_enter(ctx);
@@ -244,5 +277,83 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, 
 	if (rc == 0)
 		rc = ecg_um_launch(ctx, fn, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev, (t.bits | C) % 16u != 0, masks,
 			       result, flags, st);
+	return ecg_staged_close(ctx, &t, st, rc);
+}
+
+int ecg_agg_threshold(int k, int p)
+{
+	if (k < 1 || k > ECG_KMAX_K || p < 1 || p > ECG_KMAX_R)
+		return ecg_fail(-ECG_DER_INVAL, "agg_threshold: k=%d p=%d outside the limits k <= %d, p <= %d", k, p,
+				ECG_KMAX_K, ECG_KMAX_R);
+	/* delta (2n + 2p) C against re-encode (k + p) C; the tie goes to the delta */
+	return k > p ? (k - p) / 2 : 0;
+}
+
+int ecg_agg_masks(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S,
+		  const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
+		  void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		  const uint32_t *masks, void *result, uint32_t recalc_above, unsigned flags, void *stream)
+{
+	static const char fn[] = "agg_masks";
+	hipStream_t st;
+	int rc;
+
+	rc = ecg_um_check(fn, 1, ctx != NULL, k, p, C, S, old_cells, new_cells, parity, parity_cell_stride,
+			  parity_stripe_stride, NULL, masks, result, flags, &recalc_above);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+
+	/* nothing updated, no invalid mask */
+	rc = ecg_result_reset(result, st, "agg_masks memset");
+	if (rc || S == 0 || C == 0)
+		return rc;
+	return um_launch(ctx, fn, 1, recalc_above, k, p, C, S, old_cells, new_cells, upd_stripe_stride, parity,
+			 parity_cell_stride, parity_stripe_stride, NULL,
+			 ((uintptr_t)old_cells | (uintptr_t)new_cells | (uintptr_t)parity | (uint64_t)upd_stripe_stride |
+			  (uint64_t)parity_cell_stride | (uint64_t)parity_stripe_stride | C) % 16u != 0,
+			 masks, result, flags, st);
+}
+
+int ecg_agg_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t C, uint32_t S, void *const *cells,
+		       const uint32_t *masks, void *result, uint32_t recalc_above, unsigned flags, void *stream)
+{
+	static const char fn[] = "agg_masks_ptrs";
+	const struct ecg_clear clear[2] = {{masks, 4ull * S, "masks"}, {result, 32, "result"}};
+	struct ecg_staged t;
+	int64_t us, pc, ps;
+	hipStream_t st;
+	int rc;
+
+	rc = ecg_um_check(fn, 0, ctx != NULL, k, p, C, S, NULL, NULL, NULL, 0, 0, cells, masks, result, flags,
+			  &recalc_above);
+	if (rc)
+		return rc;
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	if (S == 0 || C == 0)	/* nothing updated, no invalid mask */
+		return ecg_result_reset(result, st, "agg_masks_ptrs memset");
+
+	rc = ecg_staged_open(ctx, fn, cells, S, (uint32_t)(2 * k + p), C, clear, 2, &t);
+	if (rc)
+		return rc;
+	/* ecg_agg_masks's own layout, as ecg_update_masks_ptrs finds
+	 * ecg_update_masks's: its launch, with no table */
+	if (ecg_um_three_groups(t.sc->pin, k, p, C, S, &us, &pc, &ps) &&
+	    !ecg_cells_overlap(masks, 4ull * S, cells[2 * k], S, ps, p, pc, C) &&
+	    !ecg_cells_overlap(result, 32, cells[2 * k], S, ps, p, pc, C)) {
+		ecg_staged_close(ctx, &t, st, 0);
+		return ecg_agg_masks(ctx, k, p, C, S, cells[0], cells[k], us, cells[2 * k], pc, ps, masks, result,
+				     recalc_above, flags, stream);
+	}
+	rc = ecg_staged_upload(&t, result, st, "agg_masks_ptrs memset", "agg_masks_ptrs cell table");
+	if (rc == 0)
+		rc = um_launch(ctx, fn, 1, recalc_above, k, p, C, S, NULL, NULL, 0, NULL, 0, 0, t.sc->dev,
+			       (t.bits | C) % 16u != 0, masks, result, flags, st);
 	return ecg_staged_close(ctx, &t, st, rc);
 }

@@ -35,6 +35,19 @@
 // block per column, grp = 64 with a few column blocks striding -- a clean
 // batch then costs S / 64 * grid.x blocks of one load each.  Column-block 0 of
 // a row counts its stripes into `result` (ecg_rows_dev.h rows_count).
+//
+// ecg_agg_masks / ecg_agg_masks_ptrs (the ecg_agg_masks* kernels below) take
+// the same walk over the same operands and choose per stripe, by the one
+// reading the host shares (ecg_kabi.h ecg_agg_route), between that delta
+// update and a re-encode of the merged stripe,
+//
+//     parity[s][r] = XOR_{j < k} g[k+r][j] * (bit j of masks[s] ? new : old)[s][j]
+//
+// which walks j = 0 .. k-1 two cells at a time, each cell loaded from the one
+// image its bit selects (an address select, not two loads), and stores each
+// parity row without loading it: (k + p) C bytes, whatever the mask names.
+// The word is wave-uniform, so the route is a scalar branch per stripe; the
+// re-encode indexes j < k by construction, never by mask bits.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -74,7 +87,8 @@ __device__ __forceinline__ uint64_t um_cell(uint32_t packed, uint32_t i, uint32_
 // differ in.  A body positions the struct on a stripe (at), binds parity row r
 // once per stripe (bind), asks per column for the row's address (par) and,
 // per set bit j of the mask (the i-th in ascending order), for the addresses
-// of the old and the new cell at the column's offset (pair).
+// of the old and the new cell at the column's offset (pair); the re-encode of
+// ecg_agg_masks asks for cell j of one image (cell).
 
 // Three strided images: every address is arithmetic on the stripe's three
 // bases, done per column, so nothing is bound.
@@ -108,6 +122,11 @@ struct um_strided {
 		*o = ob + c;
 		*n = nb + c;
 	}
+	// cell j (unpacked) of one image, the new one with fromnew
+	__device__ const uint8_t *cell(uint32_t j, uint32_t fromnew, uint64_t off) const
+	{
+		return (fromnew ? nb : ob) + (uint64_t)j * C + off;
+	}
 };
 
 // The stripe's row pt of a cell table: old cell j = pt[j], new cell j =
@@ -133,7 +152,69 @@ struct um_table {
 		*o = reinterpret_cast<const uint8_t *>(pt[j]) + off;
 		*n_ = reinterpret_cast<const uint8_t *>(pt[k + j]) + off;
 	}
+	// one entry of the row: the old or the new cell j, j < k
+	__device__ const uint8_t *cell(uint32_t j, uint32_t fromnew, uint64_t off) const
+	{
+		return reinterpret_cast<const uint8_t *>(pt[(fromnew ? k : 0u) + j]) + off;
+	}
 };
+
+// um_lanes' walk of a mask's set bits as a function, for ag_lanes: acc[r] ^=
+// tbl[r][j] * (old_j ^ new_j) at a lane's 16 bytes `off` of a column, two bits
+// at a time -- four cell loads in flight.  (um_lanes keeps the loop in its
+// body: calling this from there changes the SGPR figures of
+// ecg_update_masks_kernel, which stay those of the kernels as they were.)
+template <int RM, class Addr>
+__device__ __forceinline__ void um_delta(const Addr &A, const u32x4 *s_tbl, int rows, uint32_t m, uint64_t off,
+					 u32x4 *acc)
+{
+	using TB = mm_tbl<RM>;
+
+	for (uint32_t mm = m, i = 0; mm; i += 2) {
+		const uint32_t j0 = (uint32_t)__builtin_ctz(mm);
+		const uint8_t *o0, *n0, *o1, *n1;
+
+		A.pair(i, j0, off, &o0, &n0);
+		const u32x4 x0 = ld_g<16>(o0) ^ ld_g<16>(n0);
+		u32x4 x1 = (u32x4){0u, 0u, 0u, 0u};
+		uint32_t j1 = 0;
+
+		mm &= mm - 1u;
+		const bool two = mm != 0;
+		if (two) {
+			j1 = (uint32_t)__builtin_ctz(mm);
+			mm &= mm - 1u;
+			A.pair(i + 1u, j1, off, &o1, &n1);
+			x1 = ld_g<16>(o1) ^ ld_g<16>(n1);
+		}
+		// (the unsigned bit index times PER_J, not TB::cell's int:
+		// that one folds into another scalar sequence)
+		upd_fold<RM>(s_tbl + j0 * TB::PER_J, rows, x0, acc);
+		if (two)
+			upd_fold<RM>(s_tbl + j1 * TB::PER_J, rows, x1, acc);
+	}
+}
+
+// The merged stripe's column at the same 16 bytes: acc[r] ^= tbl[r][j] * (bit j
+// of m ? new_j : old_j) over every j < k, two cell loads in flight.
+template <int RM, class Addr>
+__device__ __forceinline__ void ag_recalc(const Addr &A, const u32x4 *s_tbl, int k, int rows, uint32_t m,
+					  uint64_t off, u32x4 *acc)
+{
+	using TB = mm_tbl<RM>;
+
+	for (uint32_t j = 0; j < (uint32_t)k; j += 2) {
+		const u32x4 x0 = ld_g<16>(A.cell(j, (m >> j) & 1u, off));
+		u32x4 x1 = (u32x4){0u, 0u, 0u, 0u};
+		const bool two = j + 1u < (uint32_t)k;
+
+		if (two)
+			x1 = ld_g<16>(A.cell(j + 1u, (m >> (j + 1u)) & 1u, off));
+		upd_fold<RM>(s_tbl + j * TB::PER_J, rows, x0, acc);
+		if (two)
+			upd_fold<RM>(s_tbl + (j + 1u) * TB::PER_J, rows, x1, acc);
+	}
+}
 
 // The lane kernels' body.  R = p parity rows (1..3 specialised; 0 =
 // runtime-shaped, 4..8 rows).  16-byte lanes only: every cell address (strided:
@@ -269,6 +350,141 @@ __device__ __forceinline__ void um_bytes(const ecg_mm_params_t &P, const uint32_
 	}
 }
 
+// ---------------------------------------------------------------------------
+// ecg_agg_masks: the same walk, the route chosen per stripe (ecg_kabi.h
+// ecg_agg_route; T = the threshold, a kernel argument).  um_read accepts and
+// counts a stripe whichever route it takes.
+// ---------------------------------------------------------------------------
+template <int R, class Addr>
+__device__ __forceinline__ void ag_lanes(const ecg_mm_params_t &P, u32x4 *s_tbl, const uint32_t *__restrict__ masks,
+					 unsigned long long *result, uint32_t grp, uint32_t T, Addr A)
+{
+	constexpr int RM = R ? R : ECG_KMAX_R;
+	const int k = (int)P.k;
+	const int rows = R ? R : (int)P.rows;
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const uint32_t lo = lane_off<16>();
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const um_read read = {masks, k};
+
+	tbl_stage<RM>(s_tbl, P, ECG_KMAX_K, k, rows);
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		uint32_t mw, m;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &mw);
+
+		while (todo) {
+			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
+			// wave-uniform: a scalar branch per stripe
+			const bool recalc = ecg_agg_route(m, k, T) == ECG_AGG_RECALC;
+
+			A.at(s);
+#pragma unroll
+			for (int r = 0; r < RM; r++)
+				if (r < rows)
+					A.bind(r);
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t off = (uint64_t)ch * CHUNK_BYTES + lo;
+				u32x4 acc[RM];
+
+				// a partial last column is a lane mask (C % 16 == 0 here)
+				if (off + 16 > C)
+					continue;
+				if (recalc) {
+					// the old parity is not read
+#pragma unroll
+					for (int r = 0; r < RM; r++)
+						acc[r] = (u32x4){0u, 0u, 0u, 0u};
+					ag_recalc<RM>(A, s_tbl, k, rows, m, off, acc);
+				} else {
+#pragma unroll
+					for (int r = 0; r < RM; r++)
+						if (r < rows)
+							acc[r] = ld_g<16>(A.par(r) + off);
+					um_delta<RM>(A, s_tbl, rows, m, off, acc);
+				}
+#pragma unroll
+				for (int r = 0; r < RM; r++)
+					if (r < rows)
+						st_g<16>(A.par(r) + off, acc[r]);
+			}
+		}
+	}
+}
+
+// The byte body: um_bytes' walk; a re-encoded stripe's parity bytes are
+// written (=) where the delta's are folded in (^=).
+template <class Addr>
+__device__ __forceinline__ void ag_bytes(const ecg_mm_params_t &P, const uint32_t *__restrict__ masks,
+					 unsigned long long *result, uint32_t grp, uint32_t T, Addr A)
+{
+	const uint64_t C = P.cell_bytes;
+	const uint32_t nchunk = (uint32_t)((C + CHUNK_BYTES - 1) / CHUNK_BYTES);
+	const int k = (int)P.k, rows = (int)P.rows;
+	const uint32_t nrow = rows_count_rows(P.nstripes, grp);
+	const um_read read = {masks, k};
+
+	for (uint32_t row = blockIdx.y; row < nrow; row += gridDim.y) {
+		uint32_t mw, m;
+		uint64_t todo = rows_scan(P.nstripes, row, grp, result, read, &mw);
+
+		while (todo) {
+			const uint32_t s = rows_next(&todo, row, grp, mw, &m);
+			const bool recalc = ecg_agg_route(m, k, T) == ECG_AGG_RECALC;
+
+			A.at(s);
+#pragma unroll
+			for (int r = 0; r < ECG_KMAX_R; r++)
+				if (r < rows)
+					A.bind(r);
+
+			for (uint32_t ch = blockIdx.x; ch < nchunk; ch += gridDim.x) {
+				const uint64_t cbase = (uint64_t)ch * CHUNK_BYTES;
+
+				for (uint64_t b = cbase + threadIdx.x; b < cbase + CHUNK_BYTES && b < C; b += BLOCK) {
+					uint32_t o[ECG_KMAX_R];
+
+					for (int r = 0; r < ECG_KMAX_R; r++)
+						o[r] = 0;
+					if (recalc) {
+						for (uint32_t j = 0; j < (uint32_t)k; j++) {
+							const uint32_t v = *A.cell(j, (m >> j) & 1u, b);
+
+#pragma unroll
+							for (int r = 0; r < ECG_KMAX_R; r++)
+								if (r < rows)
+									o[r] ^= gf_mul1(P.tbl[r][j], v);
+						}
+#pragma unroll
+						for (int r = 0; r < ECG_KMAX_R; r++)
+							if (r < rows)
+								A.par(r)[b] = (uint8_t)o[r];
+						continue;
+					}
+					for (uint32_t mm = m, i = 0; mm; mm &= mm - 1u, i++) {
+						const uint32_t j = (uint32_t)__builtin_ctz(mm);
+						const uint8_t *oc, *nc;
+
+						A.pair(i, j, b, &oc, &nc);
+						const uint32_t v = (uint32_t)*oc ^ (uint32_t)*nc;
+
+#pragma unroll
+						for (int r = 0; r < ECG_KMAX_R; r++)
+							if (r < rows)
+								o[r] ^= gf_mul1(P.tbl[r][j], v);
+					}
+#pragma unroll
+					for (int r = 0; r < ECG_KMAX_R; r++)
+						if (r < rows)
+							A.par(r)[b] ^= (uint8_t)o[r];
+				}
+			}
+		}
+	}
+}
+
 } // namespace
 
 // The entry points: the strided images P.src / P.src2 / P.dst
@@ -307,53 +523,95 @@ ecg_update_masks_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *__rest
 	um_bytes(P, masks, result, grp, um_table<ECG_KMAX_R>(cells, P.k, P.rows));
 }
 
+// ecg_agg_masks / ecg_agg_masks_ptrs: the same two layouts (never packed: the
+// re-encode needs the unnamed old cells in their slots).
+template <int R>
+__global__ void __launch_bounds__(BLOCK)
+ecg_agg_masks_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks, unsigned long long *result,
+		     uint32_t grp, uint32_t T)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, R ? R : ECG_KMAX_R)];
+
+	ag_lanes<R>(P, s_tbl, masks, result, grp, T, um_strided(P, 0));
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_agg_masks_byte_kernel(const ecg_mm_params_t P, const uint32_t *__restrict__ masks, unsigned long long *result,
+			  uint32_t grp, uint32_t T)
+{
+	ag_bytes(P, masks, result, grp, T, um_strided(P, 0));
+}
+
+template <int R>
+__global__ void __launch_bounds__(BLOCK)
+ecg_agg_masks_ptr_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells,
+			 const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp, uint32_t T)
+{
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(ECG_KMAX_K, R ? R : ECG_KMAX_R)];
+
+	ag_lanes<R>(P, s_tbl, masks, result, grp, T, um_table<R ? R : ECG_KMAX_R>(cells, P.k, R ? R : P.rows));
+}
+
+__global__ void __launch_bounds__(BLOCK)
+ecg_agg_masks_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells,
+			      const uint32_t *__restrict__ masks, unsigned long long *result, uint32_t grp, uint32_t T)
+{
+	ag_bytes(P, masks, result, grp, T, um_table<ECG_KMAX_R>(cells, P.k, P.rows));
+}
+
 // ---------------------------------------------------------------------------
-// Dispatch: one table for both layouts.  The lane instantiations, then the
-// byte kernels; the launcher reports an entry's name (strided) or pname (cell
-// table).
+// Dispatch: one table for both layouts and both calls.  The lane
+// instantiations, then the byte kernels; a launcher reports an entry's name
+// (strided) or pname (cell table), ecg_k_launch_agg_masks its aname / apname.
 // ---------------------------------------------------------------------------
+// the last argument: `packed` of the update kernels, T of the agg kernels
 typedef void (*um_fn_t)(const ecg_mm_params_t, const uint32_t *, unsigned long long *, uint32_t, uint32_t);
 typedef void (*ump_fn_t)(const ecg_mm_params_t, const uint64_t *, const uint32_t *, unsigned long long *, uint32_t);
+typedef void (*agp_fn_t)(const ecg_mm_params_t, const uint64_t *, const uint32_t *, unsigned long long *, uint32_t,
+			 uint32_t);
 
 struct umentry {
 	int r;
 	um_fn_t fn;
 	ump_fn_t pfn;
 	const char *name, *pname;
+	um_fn_t afn;
+	agp_fn_t apfn;
+	const char *aname, *apname;
 };
 
 #define UME(R_)                                                                                                        \
 	{R_, ecg_update_masks_kernel<R_>, ecg_update_masks_ptr_kernel<R_>, "ecg_update_masks_kernel<" #R_ ">",        \
-	 "ecg_update_masks_ptr_kernel<" #R_ ">"}
+	 "ecg_update_masks_ptr_kernel<" #R_ ">", ecg_agg_masks_kernel<R_>, ecg_agg_masks_ptr_kernel<R_>,              \
+	 "ecg_agg_masks_kernel<" #R_ ">", "ecg_agg_masks_ptr_kernel<" #R_ ">"}
 
 // the DAOS classes' p = 1..3 specialised, 4..8 parity rows runtime-shaped
 static const umentry g_um[] = {UME(1), UME(2), UME(3), UME(0),
 			       {-1, ecg_update_masks_byte_kernel, ecg_update_masks_ptr_byte_kernel,
-				"ecg_update_masks_byte_kernel", "ecg_update_masks_ptr_byte_kernel"}};
+				"ecg_update_masks_byte_kernel", "ecg_update_masks_ptr_byte_kernel",
+				ecg_agg_masks_byte_kernel, ecg_agg_masks_ptr_byte_kernel, "ecg_agg_masks_byte_kernel",
+				"ecg_agg_masks_ptr_byte_kernel"}};
 #define N_UM ((uint32_t)(sizeof(g_um) / sizeof(g_um[0])))
 #define UM_BYTE (N_UM - 1)
 
-extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
-					 uint64_t *result, int packed, int bytewise, int sparse,
-					 const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
+// What both launchers check and choose: the operands, the grid and its block
+// rows of *grp stripes, and the entry *id of g_um.
+static hipError_t um_plan(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+			  const uint64_t *result, int packed, int bytewise, int sparse, const ecg_launch_cfg_t *cfg,
+			  uint32_t *grp, uint32_t *gx, uint32_t *gy, uint32_t *id)
 {
-	hipStream_t st = (hipStream_t)stream;
-	uint32_t gx, gy, id = UM_BYTE;
-
-	if (p->nstripes == 0 || p->cell_bytes == 0)
-		return (int)hipSuccess;
 	if (p->k == 0 || p->k > ECG_KMAX_K || p->rows == 0 || p->rows > ECG_KMAX_R || masks == nullptr ||
 	    result == nullptr)
-		return (int)hipErrorInvalidValue;
+		return hipErrorInvalidValue;
 	if (cells_dev == nullptr && (p->src == nullptr || p->src2 == nullptr || p->dst == nullptr ||
 				     p->src_stripe_stride != p->src2_stripe_stride))
-		return (int)hipErrorInvalidValue;
+		return hipErrorInvalidValue;
 	if (cells_dev != nullptr && packed)	// a table has an address in slot j
-		return (int)hipErrorInvalidValue;
-	const uint32_t grp = sparse ? 64u : ECG_RM_DENSE_GRP;
+		return hipErrorInvalidValue;
+	*grp = sparse ? 64u : ECG_RM_DENSE_GRP;
+	rows_grid(p, *grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, gx, gy);
 
-	rows_grid(p, grp, sparse ? ECG_REPAIR_GRID_X : ECG_RM_DENSE_GRID_X, cfg, &gx, &gy);
-
+	*id = UM_BYTE;
 	if (!bytewise) {
 		// the lane kernel reads and writes dwordx4 at the cells' own addresses;
 		// those of a cell table the host has found 16-byte aligned (the table
@@ -367,13 +625,29 @@ extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_
 				al |= (uint64_t)p->dst_cell_off[r];
 		}
 		if ((al & 15u) != 0)
-			return (int)hipErrorInvalidValue;
-		for (id = 0; id < UM_BYTE; id++)
-			if (g_um[id].r == (int)p->rows || g_um[id].r == 0)
+			return hipErrorInvalidValue;
+		for (*id = 0; *id < UM_BYTE; (*id)++)
+			if (g_um[*id].r == (int)p->rows || g_um[*id].r == 0)
 				break;
-		if (id == UM_BYTE)
-			return (int)hipErrorInvalidValue;
+		if (*id == UM_BYTE)
+			return hipErrorInvalidValue;
 	}
+	return hipSuccess;
+}
+
+extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+					 uint64_t *result, int packed, int bytewise, int sparse,
+					 const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
+{
+	hipStream_t st = (hipStream_t)stream;
+	uint32_t grp, gx, gy, id;
+
+	if (p->nstripes == 0 || p->cell_bytes == 0)
+		return (int)hipSuccess;
+	const hipError_t e = um_plan(p, cells_dev, masks, result, packed, bytewise, sparse, cfg, &grp, &gx, &gy, &id);
+
+	if (e != hipSuccess)
+		return (int)e;
 	if (cells_dev == nullptr)
 		hipLaunchKernelGGL(g_um[id].fn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks, (unsigned long long *)result,
 				   grp, (uint32_t)(packed != 0));
@@ -382,5 +656,33 @@ extern "C" int ecg_k_launch_update_masks(const ecg_mm_params_t *p, const uint64_
 				   (unsigned long long *)result, grp);
 	if (kernel)
 		*kernel = cells_dev ? g_um[id].pname : g_um[id].name;
+	return (int)hipGetLastError();
+}
+
+// ecg_agg_masks / ecg_agg_masks_ptrs (declared in host/ecg_internal.h): the
+// update's operands, never packed, and the threshold T = recalc_above <= k.
+extern "C" int ecg_k_launch_agg_masks(const ecg_mm_params_t *p, const uint64_t *cells_dev, const uint32_t *masks,
+				      uint64_t *result, uint32_t recalc_above, int bytewise, int sparse,
+				      const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
+{
+	hipStream_t st = (hipStream_t)stream;
+	uint32_t grp, gx, gy, id;
+
+	if (p->nstripes == 0 || p->cell_bytes == 0)
+		return (int)hipSuccess;
+	if (recalc_above > p->k)
+		return (int)hipErrorInvalidValue;
+	const hipError_t e = um_plan(p, cells_dev, masks, result, 0, bytewise, sparse, cfg, &grp, &gx, &gy, &id);
+
+	if (e != hipSuccess)
+		return (int)e;
+	if (cells_dev == nullptr)
+		hipLaunchKernelGGL(g_um[id].afn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, masks, (unsigned long long *)result,
+				   grp, recalc_above);
+	else
+		hipLaunchKernelGGL(g_um[id].apfn, dim3(gx, gy), dim3(BLOCK), 0, st, *p, cells_dev, masks,
+				   (unsigned long long *)result, grp, recalc_above);
+	if (kernel)
+		*kernel = cells_dev ? g_um[id].apname : g_um[id].aname;
 	return (int)hipGetLastError();
 }

@@ -63,6 +63,11 @@ _SIGS = [
                                    C.c_int64, vp, vp, C.c_uint, vp]),
     ("ecg_update_masks_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
                                         C.c_uint, vp]),
+    ("ecg_agg_threshold", C.c_int, [C.c_int, C.c_int]),
+    ("ecg_agg_masks", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, vp, C.c_int64, vp, C.c_int64,
+                                C.c_int64, vp, vp, C.c_uint32, C.c_uint, vp]),
+    ("ecg_agg_masks_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), vp, vp,
+                                     C.c_uint32, C.c_uint, vp]),
     ("ecg_verify",C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, vp, C.c_int64, vp, C.c_int64,
                              C.c_int64, vp, vp, vp]),
     ("ecg_verify_cell", C.c_int, [C.c_uint32, C.c_int, C.c_int]),
@@ -448,6 +453,16 @@ def repair_row(k: int, p: int, cell: int):
 RM_SPARSE = 0x1     # ECG_RM_SPARSE
 UM_PACKED = 0x2     # ECG_UM_PACKED
 CM_ERASED, CM_SURVIVORS = 0x1, 0x2      # ECG_CM_ERASED, ECG_CM_SURVIVORS
+AGG_AUTO = 0xFFFFFFFF   # ECG_AGG_AUTO
+
+
+def agg_threshold(k: int, p: int) -> int:
+    """ecg_agg_threshold: the changed-cell count above which Context.agg_masks(AGG_AUTO)
+    re-encodes a stripe, (k - p) // 2 for k > p, else 0."""
+    n = lib().ecg_agg_threshold(k, p)
+    if n < 0:
+        raise EcgError(n, "agg_threshold")
+    return n
 
 
 def erasure_sets(k: int, p: int) -> int:
@@ -669,6 +684,25 @@ class Context:
         only), UM_PACKED is refused."""
         _chk(lib().ecg_update_masks_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks, result,
                                          flags, stream), "update_masks_ptrs")
+
+    def agg_masks(self, k: int, p: int, cell_bytes: int, nstripes: int, old: int, new: int,
+                  upd_stripe_stride: int, parity: int, parity_cell_stride: int, parity_stripe_stride: int,
+                  masks: int, result: int, recalc_above: int = AGG_AUTO, flags: int = 0, stream=None):
+        """ecg_agg_masks: update_masks() with a route per stripe -- a stripe whose mask names more
+        than recalc_above cells (0..k, or AGG_AUTO = agg_threshold(k, p)) is re-encoded from its
+        merged cells (bit j set: new cell j, else old cell j) without reading its old parity, any
+        other gets update_masks()'s delta.  Operands, masks and result as update_masks()'s; flags:
+        RM_SPARSE, UM_PACKED is refused."""
+        _chk(lib().ecg_agg_masks(self.h, k, p, cell_bytes, nstripes, old, new, upd_stripe_stride, parity,
+                                 parity_cell_stride, parity_stripe_stride, masks, result, recalc_above, flags, stream),
+             "agg_masks")
+
+    def agg_masks_ptrs(self, k: int, p: int, cell_bytes: int, nstripes: int, cells: Sequence[int] | None,
+                       masks: int, result: int, recalc_above: int = AGG_AUTO, flags: int = 0, stream=None):
+        """ecg_agg_masks_ptrs: agg_masks() over the table update_masks_ptrs() takes (copied before
+        the call returns)."""
+        _chk(lib().ecg_agg_masks_ptrs(self.h, k, p, cell_bytes, nstripes, self._cell_table(cells), masks, result,
+                                      recalc_above, flags, stream), "agg_masks_ptrs")
 
     def verify(self, k: int, p: int, cell_bytes: int, nstripes: int, data: int, data_stripe_stride: int,
                parity: int, parity_cell_stride: int, parity_stripe_stride: int, status: int, result: int,

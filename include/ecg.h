@@ -284,6 +284,78 @@ int ecg_update_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uin
 			  void *const *cells, const uint32_t *masks, void *result,
 			  unsigned flags, void *stream);
 
+/* ecg_update_masks with a ROUTE PER STRIPE: the delta update for a stripe that
+ * changed few cells, a re-encode of the merged stripe for one that changed
+ * many -- the choice aggregation makes per stripe between agg_update_parity
+ * and agg_recalc_parity / a full-stripe encode (ref:src/object/
+ * srv_ec_aggregate.c:1006-1138), made on the device from the mask words, so a
+ * batch of mixed change counts stays one launch of the chain ecg_csum_extents
+ * x2 -> ecg_csum_mask -> ecg_agg_masks -> ecg_csum_updated.  The delta moves
+ * (2n + 2p) * cell_bytes for n changed cells, the re-encode (k + p) *
+ * cell_bytes.
+ * ecg_agg_masks takes ecg_update_masks's operands and ecg_agg_masks_ptrs
+ * ecg_update_masks_ptrs's: old_cells, new_cells, parity, the three strides
+ * (negative included), the client and the recovery layout, the table row of
+ * 2k + p addresses and its staging (free when the call returns), masks,
+ * result, ECG_RM_SPARSE, lane and byte kernels, ecg_set_launch, telemetry --
+ * all as documented there.  What differs, for stripe s with m = masks[s], n =
+ * popcount(m) and the threshold T:
+ *   m == 0                    the stripe is untouched and not counted
+ *   a bit at or above k set   untouched; counted in result[3] and result[1]
+ *   1 <= n <= T   (delta)     byte for byte what ecg_update_masks leaves for
+ *                             the stripe; only the named old and new cells and
+ *                             the parity are read
+ *   n > T         (recalc)    parity_r = XOR_{j<k} g[k+r][j] * (bit j of m ?
+ *                             new_j : old_j) for r < p: byte for byte what
+ *                             ecg_encode writes for the merged stripe.  THE OLD
+ *                             PARITY IS NOT READ.  All k data cells are read,
+ *                             each from one image: never both images of a cell,
+ *                             never an unnamed new cell
+ * T = recalc_above when it is 0 .. k: 0 re-encodes every stripe with work, k
+ * none (the call is then ecg_update_masks).  ECG_AGG_AUTO: T =
+ * ecg_agg_threshold(k, p) = (k - p) / 2 for k > p, else 0 -- the break-even of
+ * the two traffic figures, a tie going to the delta.  Any other value is
+ * -ECG_DER_INVAL.  ecg_agg_threshold is host arithmetic (-ECG_DER_INVAL outside
+ * k 1..16, p 1..8).
+ * What follows from the two routes:
+ *  - They agree only when the stored parity matched the old data.  A recalc
+ *    stripe comes out consistent whatever its old parity held; a delta stripe
+ *    carries an old inconsistency forward.
+ *  - old_cells == new_cells is allowed: delta stripes stay as they were,
+ *    recalc stripes are re-encoded from the old data.
+ *  - THE CALLER'S CONTRACT WIDENS (not checked): NO OLD OR NEW DATA CELL OF ANY
+ *    STRIPE, NAMED BY ITS MASK OR NOT, MAY OVERLAP A PARITY CELL OF THE BATCH.
+ *    (The recovery layout, old_cells = stripes, keeps it: data and parity cells
+ *    interleave without sharing a byte.)
+ *  - ECG_UM_PACKED is refused in both forms (-ECG_DER_INVAL): the recalc route
+ *    needs the unnamed old cells in their slots.
+ * result: ecg_update_masks's four words with the same meaning whichever route
+ * a stripe took -- {stripes updated, lowest invalid, cells named by the
+ * updated stripes, invalid stripes} -- so ecg_csum_updated / _ptrs follow with
+ * the same masks; {0, UINT64_MAX, 0, 0} for nstripes == 0 or cell_bytes == 0.
+ * Which route a stripe took follows from its mask and T and is not reported.
+ * All 2^32 mask values are safe: the recalc route indexes j < k, never by mask
+ * bits.
+ * -ECG_DER_INVAL, prefixed "agg_masks:" / "agg_masks_ptrs:", in the order of
+ * ecg_update_masks / ecg_update_masks_ptrs with the ECG_UM_PACKED refusal and
+ * the recalc_above range right after the flags check (before masks, result,
+ * the operands and the context).
+ * Kernels: ecg_agg_masks_kernel<R> / ecg_agg_masks_byte_kernel, over a table
+ * ecg_agg_masks_ptr_kernel<R> / ecg_agg_masks_ptr_byte_kernel (ecg_last_kernel);
+ * a table that is three strided groups and passes the strided checks IS
+ * ecg_agg_masks, as for ecg_update_masks_ptrs.  One launch; update_cells /
+ * update_bytes are not advanced. */
+#define ECG_AGG_AUTO 0xffffffffu
+int ecg_agg_threshold(int k, int p);
+int ecg_agg_masks(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		  const void *old_cells, const void *new_cells, int64_t upd_stripe_stride,
+		  void *parity, int64_t parity_cell_stride, int64_t parity_stripe_stride,
+		  const uint32_t *masks, void *result, uint32_t recalc_above,
+		  unsigned flags, void *stream);
+int ecg_agg_masks_ptrs(ecg_ctx_t *ctx, int k, int p, uint64_t cell_bytes, uint32_t nstripes,
+		       void *const *cells, const uint32_t *masks, void *result,
+		       uint32_t recalc_above, unsigned flags, void *stream);
+
 /* Parity consistency check: does the stored parity of every stripe still
  * match its stored data -- what the EC branch of the object verify path
  * answers by re-encoding into scratch parity and memcmp

@@ -37,6 +37,13 @@ report`).  Needs no GPU.
       (remarks of ecg_update_masks_kernels.hip), SGPRs spilled into VGPR lanes listed;
       exit 1 if one uses scratch.  NEW BASE pairs as for --repair (upd_fold
       moved into ecg_mm_dev.h)
+  python tools/fused_resources.py --agg-masks UM.txt [BASE.txt]
+      the ecg_agg_masks kernels, strided and cell-table (ptr) alike (remarks
+      of ecg_update_masks_kernels.hip, which holds them), SGPRs spilled into
+      VGPR lanes listed; exit 1 if one uses scratch.  With BASE.txt (the
+      remarks of the same file from the tree before): every kernel of BASE
+      -- the ecg_update_masks kernels -- must show identical figures in
+      UM.txt (exit 1 on any difference)
   python tools/fused_resources.py --kept NEW.txt BASE.txt [NEW.txt BASE.txt]...
       a refactor's check over any kernel files: every kernel of each BASE
       found by name in its NEW with VGPRs, AGPRs, scratch and LDS equal or
@@ -128,6 +135,7 @@ def verify_table(verify_txt, product_txt=None):
 REPAIR = re.compile(r"_Z\d+(ecg_repair_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 RECOVER_MASKS = re.compile(r"_Z\d+(ecg_recover_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)ELi(\d+)EE)?")
 UPDATE_MASKS = re.compile(r"_Z\d+(ecg_update_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
+AGG_MASKS = re.compile(r"_Z\d+(ecg_agg_masks_(?:ptr_)?(?:byte_)?kernel)(?:ILi(\d+)EE)?()")
 ANY = re.compile(r"(\S+)()()")
 
 
@@ -241,6 +249,9 @@ def main():
         return repair_table(*args, pattern=RECOVER_MASKS, what="recover_masks") | bad
     if sys.argv[1] == "--update-masks":
         return repair_table(*sys.argv[2:], pattern=UPDATE_MASKS, what="update_masks")
+    if sys.argv[1] == "--agg-masks":
+        bad = kept_identical(sys.argv[2], sys.argv[3]) if len(sys.argv) > 3 else 0
+        return repair_table(sys.argv[2], pattern=AGG_MASKS, what="agg_masks") | bad
     new = parse(sys.argv[1])
     base = parse(sys.argv[2]) if len(sys.argv) > 2 else None
     bad = 0
