@@ -720,8 +720,23 @@ uint32_t ecg_k_align_granule(const ecg_mm_params_t *p);
  * with an input off a 16-byte boundary (16-byte lanes, funnel-shifted); 1 =
  * an input at any byte -- with outputs at any byte in the last three (stored
  * misaligned, so they need the device's unaligned access mode); 0 = the
- * byte-granular kernel (ecg_ptrs.c ptr_granule). */
+ * byte-granular kernel (ecg_ptrs.c ptr_granule).
+ * lens_dev == NULL (spans_dev NULL, nspans = max_cols = 0): every cell is
+ * p->cell_bytes long.  Otherwise ecg_matmul_ptrs_lens: the cells of stripe s
+ * are lens_dev[s] bytes long, and the work is the nspans records spans_dev[i] =
+ * stripe | (uint64_t)first column << 32 (4 KiB columns): span i covers at most
+ * ECG_LENS_SPAN_COLS columns of its stripe's cells from that column on, the
+ * spans of a stripe cover its cells once, a stripe of length 0 has none (its
+ * table row is never read).  max_cols = the most columns a span holds, 1 ..
+ * ECG_LENS_SPAN_COLS (hipErrorInvalidValue otherwise): grid.x.  p->cell_bytes
+ * is then the OR of every length (its low bits choose the lanes as a cell
+ * size's do; 0 = nothing to launch) and the kernels read neither it nor
+ * p->nstripes.  All three arrays are device memory, read only for the launch.
+ * *kernel: ecg_mm_ptr_kernel<k,rows[,gG]> / ecg_mm_ptr_byte_kernel, or their
+ * ecg_mm_ptr_lens_* counterparts. */
+#define ECG_LENS_SPAN_COLS 16u
 int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t *cells_dev, int granule,
+			     const uint64_t *lens_dev, const uint64_t *spans_dev, uint32_t nspans, uint32_t max_cols,
 			     const ecg_launch_cfg_t *cfg, void *stream, const char **kernel);
 /* Per-request delta updates through a pointer table (the batching queue's
  * device-cell aggregation updates, ecg_update_ptrs):  item s of the launch,

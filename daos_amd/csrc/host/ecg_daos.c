@@ -415,6 +415,97 @@ int ecg_obj_ec_singv_encode(uint32_t oc_id, uint64_t iod_size, const unsigned ch
 	return rc;
 }
 
+int ecg_obj_ec_singv_encode_dev(ecg_ctx_t *ctx, uint32_t oc_id, uint32_t nvalues, const uint64_t *iod_sizes,
+				void *const *values, void *const *parity, void *stream)
+{
+	unsigned char en[(ECG_MAX_K + ECG_MAX_P) * ECG_MAX_K];
+	struct ecg_scratch_slot *sc = NULL;
+	uint64_t *lens = NULL, nspans = 0, ngather = 0, gbytes = 0, zmax = 0;
+	size_t seg_off, zero_off;
+	uint32_t max_cols = 0, i;
+	hipStream_t st;
+	int k, p, rc;
+
+	if (ecg_obj_ec_class_kp(oc_id, &k, &p))
+		return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: oc_id 0x%x is not an EC class", oc_id);
+	if (nvalues && (iod_sizes == NULL || values == NULL || parity == NULL))
+		return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: NULL argument");
+	for (i = 0; i < nvalues; i++) {
+		if (iod_sizes[i] == 0)
+			return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: value %u: zero iod_size", i);
+		if (iod_sizes[i] >= ECG_LENS_MAX_BYTES)
+			return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: value %u: iod_size %llu", i,
+					(unsigned long long)iod_sizes[i]);
+		if (values[i] == NULL)
+			return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: value %u: NULL value", i);
+		for (int r = 0; r < p; r++)
+			if (parity[(size_t)i * p + r] == NULL)
+				return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: value %u: NULL parity cell %d", i, r);
+	}
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "singv_encode_dev: NULL context");
+	if (nvalues == 0)
+		return 0;
+	lens = malloc((size_t)nvalues * sizeof(*lens));
+	if (lens == NULL)
+		return ecg_fail(-ECG_DER_NOMEM, "singv_encode_dev: malloc");
+	/* value i: nfull whole cells in place, then the cell that straddles its
+	 * end (gathered, 16-byte aligned slots), then cells of padding alone */
+	for (i = 0; i < nvalues; i++) {
+		const uint64_t cb = ecg_obj_ec_singv_cell_bytes(oc_id, iod_sizes[i]);
+		const uint64_t nfull = iod_sizes[i] / cb, rem = iod_sizes[i] % cb;
+
+		lens[i] = cb;
+		if (rem) {
+			ngather++;
+			gbytes += (cb + 15) & ~15ull;
+		}
+		if (nfull + (rem != 0) < (uint64_t)k && cb > zmax)
+			zmax = cb;
+	}
+	zmax = (zmax + 255) & ~255ull;
+	(void)ecg_lens_plan(lens, nvalues, &nspans, &max_cols);
+	ecg_gen_cauchy1(k, p, en);	/* the codec's matrix, ref:src/object/obj_class.c:614 */
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		goto out;
+	st = ecg_pick_stream(ctx, stream);
+	/* slot layout: [table, lengths, spans | gather segments | zeros, gathered cells (dev)] */
+	seg_off = (ecg_lens_table_bytes(nvalues, k + p, nspans) + 255) & ~(size_t)255;
+	zero_off = seg_off + ((ngather * sizeof(ecg_copy_seg_t) + 255) & ~(size_t)255);
+
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, zero_off, zero_off + zmax + gbytes, &sc);
+	if (rc == 0) {
+		struct ecg_segs segs = {(ecg_copy_seg_t *)((unsigned char *)sc->pin + seg_off), 0, ngather, 0, 1};
+		const uint64_t zeros = (uint64_t)(uintptr_t)sc->dev + zero_off;
+		uint64_t *tab = sc->pin, g = zeros + zmax;
+
+		for (i = 0; i < nvalues && rc == 0; i++) {
+			const uint64_t cb = lens[i], v = (uint64_t)(uintptr_t)values[i];
+			const uint64_t nfull = iod_sizes[i] / cb, rem = iod_sizes[i] % cb;
+			uint64_t *row = tab + (size_t)i * (k + p);
+
+			for (int j = 0; j < k; j++)
+				row[j] = (uint64_t)j < nfull ? v + j * cb : (uint64_t)j == nfull && rem ? g : zeros;
+			for (int r = 0; r < p; r++)
+				row[k + r] = (uint64_t)(uintptr_t)parity[(size_t)i * p + r];
+			if (rem) {
+				rc = ecg_segs_add(&segs, g, v + nfull * cb, rem);
+				g += (cb + 15) & ~15ull;
+			}
+		}
+		memcpy(tab + (size_t)nvalues * (k + p), lens, (size_t)nvalues * sizeof(*lens));
+		if (rc == 0)
+			rc = ecg_lens_launch(ctx, sc, k, p, &en[k * k], nvalues, nspans, max_cols, st, &segs, seg_off,
+					     zero_off, zmax + gbytes);
+	}
+	pthread_mutex_unlock(&ctx->lock);
+out:
+	free(lens);
+	return rc;
+}
+
 /* ---- stripe / index math, ref:src/object/obj_ec.h:271-350 ---- */
 uint64_t ecg_obj_ec_stripe_rec_nr(uint32_t k, uint64_t e_len)
 {

@@ -147,6 +147,29 @@ int ecg_table_upload(struct ecg_scratch_slot *sc, size_t bytes, hipStream_t st, 
  * either.  Returns rc, or the event's failure when rc was 0. */
 int ecg_table_done(struct ecg_scratch_slot *sc, hipStream_t st, int rc);
 
+/* The launch of ecg_matmul_ptrs_lens over a slot its caller has filled
+ * (ecg_ptrs.c; ctx->lock held), shared with ecg_obj_ec_singv_encode_dev
+ * (ecg_daos.c).  Slot layout, pinned and device alike:
+ *   [0, S*n*8)      the cell table, n = k + rows entries per stripe (a stripe of
+ *                   length 0: zeros)
+ *   then S*8        the lengths (each below ECG_LENS_MAX_BYTES: a span's first
+ *                   column is a 32-bit word)
+ *   then nspans*8   the span records, written here -- ecg_lens_table_bytes()
+ *                   in all, nspans and max_cols being ecg_lens_plan's
+ *   seg_off         with `gather` (NULL: none), its segments; they travel in
+ *                   the same upload and run before the product
+ *   zero_off        device only: zero_bytes (0: none) set to zero before the
+ *                   gather, for cells the table points into it
+ * One upload, the memset, the gather, one product launch -- the fixed-length
+ * kernel through launch tuner when every length is the same and none is 0 --
+ * and ecg_table_done on every way out once the upload is queued. */
+#define ECG_LENS_MAX_BYTES (1ull << 44)
+struct ecg_segs;
+size_t ecg_lens_table_bytes(uint32_t S, int n, uint64_t nspans);
+int ecg_lens_launch(ecg_ctx_t *ctx, struct ecg_scratch_slot *sc, int k, int rows, const unsigned char *coef,
+		    uint32_t S, uint64_t nspans, uint32_t max_cols, hipStream_t st, const struct ecg_segs *gather,
+		    size_t seg_off, size_t zero_off, size_t zero_bytes);
+
 /* batched segment copies (ecg_sgl.c).  A fixed list (cap preset, fixed = 1)
  * writes into caller memory and fails instead of growing. */
 struct ecg_segs {

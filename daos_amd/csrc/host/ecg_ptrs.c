@@ -206,20 +206,19 @@ static int launch_ptrs(const ecg_mm_params_t *p, const ecg_launch_cfg_t *cfg, vo
 {
 	const struct ptr_launch_arg *a = arg;
 
-	return ecg_k_launch_matmul_ptrs(p, a->cells_dev, a->granule, cfg, stream, kernel);
+	return ecg_k_launch_matmul_ptrs(p, a->cells_dev, a->granule, NULL, NULL, 0, 0, cfg, stream, kernel);
 }
 
-/* The product over the table a->cells_dev, through the launch tuner like the
- * strided product: wide stripes probe the blocks-per-CU cap per (shape,
- * pointer-table layout). */
-static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k, int rows, const unsigned char *coef,
-			  uint64_t C, uint32_t S, hipStream_t st, const char **kernel)
+/* Launch parameters of a pointer-table product: the shape and coef as perm
+ * tables (the operand fields stay zero); free() it. */
+static ecg_mm_params_t *ptr_params(int k, int rows, const unsigned char *coef, uint64_t C, uint32_t S)
 {
 	ecg_mm_params_t *prm = calloc(1, sizeof(*prm));
-	int ke;
 
-	if (prm == NULL)
-		return ecg_fail(-ECG_DER_NOMEM, "matmul_ptrs: calloc");
+	if (prm == NULL) {
+		(void)ecg_fail(-ECG_DER_NOMEM, "matmul_ptrs: calloc");
+		return NULL;
+	}
 	ecg_gf_init();
 	prm->cell_bytes = C;
 	prm->nstripes = S;
@@ -228,6 +227,20 @@ static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k,
 	for (int r = 0; r < rows; r++)
 		for (int j = 0; j < k; j++)
 			ecg_build_ptbl(coef[(size_t)r * k + j], &prm->tbl[r][j]);
+	return prm;
+}
+
+/* The product over the table a->cells_dev, through the launch tuner like the
+ * strided product: wide stripes probe the blocks-per-CU cap per (shape,
+ * pointer-table layout). */
+static int launch_product(ecg_ctx_t *ctx, const struct ptr_launch_arg *a, int k, int rows, const unsigned char *coef,
+			  uint64_t C, uint32_t S, hipStream_t st, const char **kernel)
+{
+	ecg_mm_params_t *prm = ptr_params(k, rows, coef, C, S);
+	int ke;
+
+	if (prm == NULL)
+		return -ECG_DER_NOMEM;
 	ke = ecg_tune_launch_fn(ctx, prm, (uint32_t)a->granule, ECG_TUNE_LAYOUT_PTRS, launch_ptrs, a, st, kernel);
 	free(prm);
 	return ke ? ecg_hip_fail((hipError_t)ke, "pointer-table kernel launch") : 0;
@@ -303,6 +316,159 @@ int ecg_matmul_ptrs(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, 
 	if (rc == 0) {
 		memcpy(sc->pin, cells, n * sizeof(uint64_t));
 		rc = launch_table(ctx, sc, k, rows, coef, cell_bytes, nstripes, st, NULL, 0);
+	}
+	pthread_mutex_unlock(&ctx->lock);
+	return rc;
+}
+
+/* ---- the pointer-table product with a cell length per stripe ------------ */
+
+#define LENS_COL 4096u	/* the kernels' column (ecg_mm_dev.h CHUNK_BYTES) */
+_Static_assert(ECG_LENS_SPAN_BYTES == ECG_LENS_SPAN_COLS * LENS_COL, "a span is ECG_LENS_SPAN_COLS columns");
+
+int ecg_lens_plan(const uint64_t *cell_bytes, uint32_t nstripes, uint64_t *nspans, uint32_t *max_cols)
+{
+	uint64_t n = 0, mc = 0;
+
+	if (nstripes && (cell_bytes == NULL || nspans == NULL || max_cols == NULL))
+		return ecg_fail(-ECG_DER_INVAL, "lens_plan: NULL argument");
+	for (uint32_t s = 0; s < nstripes; s++) {
+		const uint64_t L = cell_bytes[s];
+		const uint64_t cols = L / LENS_COL + (L % LENS_COL != 0);
+
+		n += L / ECG_LENS_SPAN_BYTES + (L % ECG_LENS_SPAN_BYTES != 0);
+		if (cols > mc)
+			mc = cols < ECG_LENS_SPAN_COLS ? cols : ECG_LENS_SPAN_COLS;
+	}
+	if (nspans)
+		*nspans = n;
+	if (max_cols)
+		*max_cols = (uint32_t)mc;
+	return 0;
+}
+
+size_t ecg_lens_table_bytes(uint32_t S, int n, uint64_t nspans)
+{
+	return ((size_t)S * (size_t)(n + 1) + (size_t)nspans) * sizeof(uint64_t);
+}
+
+int ecg_lens_launch(ecg_ctx_t *ctx, struct ecg_scratch_slot *sc, int k, int rows, const unsigned char *coef,
+		    uint32_t S, uint64_t nspans, uint32_t max_cols, hipStream_t st, const struct ecg_segs *gather,
+		    size_t seg_off, size_t zero_off, size_t zero_bytes)
+{
+	const size_t n = (size_t)(k + rows);
+	uint64_t *tab = sc->pin, *lens = tab + (size_t)S * n, *spans = lens + S;
+	const uint64_t *dev = sc->dev;
+	const struct ptr_launch_arg a = {dev, ptr_granule(tab, S, k, rows, (int)ctx->cfg.no_unaligned)};
+	size_t tbytes = ecg_lens_table_bytes(S, (int)n, nspans);
+	uint64_t lor = 0, at = 0;
+	const char *kernel = NULL;
+	int rc, equal = 1;
+
+	for (uint32_t s = 0; s < S; s++) {
+		lor |= lens[s];
+		equal &= lens[s] == lens[0] && lens[s] != 0;
+		for (uint64_t col = 0; col * LENS_COL < lens[s] && at < nspans; col += ECG_LENS_SPAN_COLS)
+			spans[at++] = s | col << 32;
+	}
+	if (at != nspans || nspans > UINT32_MAX)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: %llu spans", (unsigned long long)nspans);
+	if (gather && gather->n)
+		tbytes = seg_off + gather->n * sizeof(ecg_copy_seg_t);
+	rc = ecg_table_upload(sc, tbytes, st, "pointer table");
+	if (rc)
+		return rc;
+	/* the fetch is queued: whatever fails below, out through ecg_table_done */
+	if (zero_bytes) {
+		const hipError_t e = hipMemsetAsync((unsigned char *)sc->dev + zero_off, 0, zero_bytes, st);
+
+		if (e != hipSuccess)
+			rc = ecg_hip_fail(e, "matmul_ptrs_lens: padding memset");
+	}
+	if (rc == 0 && gather && gather->n)
+		rc = ecg_segs_launch(gather, (unsigned char *)sc->dev + seg_off, st);
+	if (rc == 0 && equal) {
+		/* one length: the fixed-length kernel over the same table */
+		rc = launch_product(ctx, &a, k, rows, coef, lens[0], S, st, &kernel);
+	} else if (rc == 0) {
+		/* cell_bytes = the OR of the lengths: the launcher's lane choice */
+		ecg_mm_params_t *prm = ptr_params(k, rows, coef, lor, S);
+
+		if (prm == NULL) {
+			rc = -ECG_DER_NOMEM;
+		} else {
+			const int ke = ecg_k_launch_matmul_ptrs(prm, dev, a.granule, dev + (size_t)S * n,
+								dev + (size_t)S * n + S, (uint32_t)nspans, max_cols,
+								&ctx->cfg, (void *)st, &kernel);
+
+			free(prm);
+			if (ke)
+				rc = ecg_hip_fail((hipError_t)ke, "pointer-table kernel launch");
+		}
+	}
+	rc = ecg_table_done(sc, st, rc);
+	if (rc == 0) {
+		ECG_STAT_ADD(ctx, launches, 1);
+		ecg_set_last_kernel(kernel);
+	}
+	return rc;
+}
+
+int ecg_matmul_ptrs_lens(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef, uint32_t nstripes,
+			 void *const *cells, const uint64_t *cell_bytes, void *stream)
+{
+	const size_t n = (size_t)(k + rows);
+	struct ecg_scratch_slot *sc = NULL;
+	uint64_t nspans = 0;
+	uint32_t max_cols = 0;
+	hipStream_t st;
+	size_t bytes;
+	int rc, equal = 1;
+
+	if (k < 1 || k > ECG_KMAX_K || rows < 1 || rows > ECG_KMAX_R)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: k=%d rows=%d (max %d x %d)", k, rows, ECG_KMAX_K,
+				ECG_KMAX_R);
+	if (coef == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: NULL coef");
+	if (nstripes && cell_bytes == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: NULL cell_bytes");
+	if (ctx == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: NULL context");
+	if (nstripes && cells == NULL)
+		return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: NULL cells");
+	(void)ecg_lens_plan(cell_bytes, nstripes, &nspans, &max_cols);
+	if (nspans == 0)
+		return 0;
+	for (uint32_t s = 0; s < nstripes; s++) {
+		equal &= cell_bytes[s] == cell_bytes[0] && cell_bytes[s] != 0;
+		if (cell_bytes[s] >= ECG_LENS_MAX_BYTES)
+			return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: cell_bytes[%u] = %llu", s,
+					(unsigned long long)cell_bytes[s]);
+		for (size_t j = 0; j < n && cell_bytes[s]; j++)
+			if (cells[s * n + j] == NULL)
+				return ecg_fail(-ECG_DER_INVAL, "matmul_ptrs_lens: NULL cell %zu", s * n + j);
+	}
+	if (equal)	/* one length and no stripe skipped: ecg_matmul_ptrs, its affine shortcut included */
+		return ecg_matmul_ptrs(ctx, k, rows, coef, cell_bytes[0], nstripes, cells, stream);
+	rc = ecg_ctx_enter(ctx);
+	if (rc)
+		return rc;
+	st = ecg_pick_stream(ctx, stream);
+	bytes = ecg_lens_table_bytes(nstripes, (int)n, nspans);
+	pthread_mutex_lock(&ctx->lock);
+	rc = ecg_scratch_reserve(ctx, bytes, bytes, &sc);
+	if (rc == 0) {
+		uint64_t *tab = sc->pin;
+
+		/* a skipped stripe's entries are not read: its row is staged as zeros */
+		for (uint32_t s = 0; s < nstripes; s++) {
+			if (cell_bytes[s])
+				memcpy(tab + s * n, cells + s * n, n * sizeof(uint64_t));
+			else
+				memset(tab + s * n, 0, n * sizeof(uint64_t));
+		}
+		memcpy(tab + nstripes * n, cell_bytes, (size_t)nstripes * sizeof(uint64_t));
+		rc = ecg_lens_launch(ctx, sc, k, rows, coef, nstripes, nspans, max_cols, st, NULL, 0, 0, 0);
 	}
 	pthread_mutex_unlock(&ctx->lock);
 	return rc;

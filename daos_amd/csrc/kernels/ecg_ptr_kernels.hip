@@ -160,6 +160,142 @@ ecg_mm_ptr_byte_kernel(const ecg_mm_params_t P, const uint64_t *cells)
 }
 
 // ---------------------------------------------------------------------------
+// The same product with a cell length per stripe (ecg_matmul_ptrs_lens):
+// lens[s] = the bytes of every cell of stripe s.  The host cuts each stripe
+// into spans of at most ECG_LENS_SPAN_COLS columns and lists them, spans[i] =
+// {stripe (low dword), first column (high dword)} (ecg_kabi.h); grid.y walks
+// the spans (strided past 65535), grid.x the columns of a span.  A block reads
+// its span's record, the stripe's length and its k + rows addresses with
+// wave-uniform (scalar) loads once per span, so a batch of small values is one
+// block per value with no search and a long cell one block per column, as in
+// the fixed-length kernel.  P.cell_bytes and P.nstripes are not read: in
+// pointer mode neither mm_ptr_item nor mm_compute uses them.
+// ---------------------------------------------------------------------------
+
+// columns of the span starting at column col0 of a cell of C bytes (0: none)
+__device__ __forceinline__ uint32_t lens_span_cols(uint64_t C, uint32_t col0)
+{
+	const uint64_t nchunk = (C + CHUNK_BYTES - 1) / CHUNK_BYTES;
+
+	if (nchunk <= col0)
+		return 0;
+	return nchunk - col0 < ECG_LENS_SPAN_COLS ? (uint32_t)(nchunk - col0) : ECG_LENS_SPAN_COLS;
+}
+
+// One column of stripe s (table row pt, addresses base[]) at cbase of cells
+// of C bytes: the column code of ecg_mm_ptr_kernel, which keeps its own
+// inlined copy (its schedule is measured as it stands).
+template <int KM, int RM, int G>
+__device__ __forceinline__ void mm_ptr_col(const ecg_mm_params_t &P, const u32x4 *s_tbl, int k, int rows,
+					   const uint64_t *pt, const uint64_t *base, uint32_t s, uint64_t cbase,
+					   uint64_t C, uint32_t lo)
+{
+	uint64_t a[KM + RM];
+	uint32_t z = 0;
+
+#pragma unroll
+	for (int j = 0; j < KM + RM; j++) {
+		if (j < k || (j >= KM && j - KM < rows)) {
+			a[j] = base[j] + cbase;
+			asm volatile("" : "+s"(a[j]));
+		}
+	}
+	asm volatile("" : "+v"(z));
+	const u32x4 *tb = s_tbl + z;
+	if (cbase + CHUNK_BYTES <= C) {
+		mm_ptr_item<KM, RM, G>(P, tb, k, rows, s, cbase, lo, a);
+	} else if constexpr (G == 16) {
+		if (cbase + lo + 16 <= C)	// every length % 16 == 0 on this path
+			mm_ptr_item<KM, RM, G>(P, tb, k, rows, s, cbase, lo, a);
+	} else {
+#pragma nounroll
+		for (int i = 0; i < 4; i++) {
+			const uint64_t off = cbase + lo + elem_off<G>(i);
+
+			if (off < C)
+				mm_ptr_bytes<KM, RM>(tb, k, rows, pt, off, (int)(C - off < 4 ? C - off : 4));
+		}
+	}
+}
+
+template <int K, int R, int G>
+__global__ void __launch_bounds__(BLOCK, ECG_MM_WPE(K, R, G) ? ECG_MM_WPE(K, R, G) : 1)
+ecg_mm_ptr_lens_kernel(const ecg_mm_params_t P, const uint64_t *__restrict__ cells,
+		       const uint64_t *__restrict__ lens, const uint64_t *__restrict__ spans, uint32_t nspans)
+{
+	constexpr int KM = K ? K : ECG_KMAX_K;
+	constexpr int RM = R ? R : ECG_KMAX_R;
+	__shared__ u32x4 s_tbl[ECG_TBL_WORDS(KM, RM)];
+	const int k = K ? K : (int)P.k;
+	const int rows = R ? R : (int)P.rows;
+	const uint32_t lo = lane_off<G>();
+	uint32_t sp = blockIdx.y;
+
+	// a block whose x is past the columns of every span of its row leaves
+	// before the table staging (a batch of small values under one long one)
+	for (; sp < nspans; sp += gridDim.y) {
+		const uint64_t rec = spans[sp];
+
+		if (blockIdx.x < lens_span_cols(lens[(uint32_t)rec], (uint32_t)(rec >> 32)))
+			break;
+	}
+	if (sp >= nspans)
+		return;
+	tbl_stage<RM>(s_tbl, P, KM, k, rows);
+
+	for (; sp < nspans; sp += gridDim.y) {
+		const uint64_t rec = spans[sp];
+		const uint32_t s = (uint32_t)rec, col0 = (uint32_t)(rec >> 32);
+		const uint64_t C = lens[s];
+		const uint32_t ncol = lens_span_cols(C, col0);
+		const uint64_t *pt = cells + (uint64_t)s * (uint32_t)(k + rows);
+		uint64_t base[KM + RM];
+
+		if (blockIdx.x >= ncol)
+			continue;
+#pragma unroll
+		for (int j = 0; j < KM + RM; j++)
+			if (j < k || (j >= KM && j - KM < rows))
+				base[j] = pt[j < KM ? j : k + (j - KM)];
+		for (uint32_t c = blockIdx.x; c < ncol; c += gridDim.x)
+			mm_ptr_col<KM, RM, G>(P, s_tbl, k, rows, pt, base, s, (uint64_t)(col0 + c) * CHUNK_BYTES, C, lo);
+	}
+}
+
+// Any alignment and length: a block per span, one byte per lane (launch
+// variant 2, and operands the device cannot serve as dwords).
+__global__ void __launch_bounds__(BLOCK)
+ecg_mm_ptr_lens_byte_kernel(const ecg_mm_params_t P, const uint64_t *cells, const uint64_t *lens,
+			    const uint64_t *spans, uint32_t nspans)
+{
+	const int k = (int)P.k, rows = (int)P.rows;
+
+	for (uint32_t sp = blockIdx.x; sp < nspans; sp += gridDim.x) {
+		const uint64_t rec = spans[sp];
+		const uint32_t s = (uint32_t)rec;
+		const uint64_t C = lens[s], b0 = (rec >> 32) * CHUNK_BYTES;
+		const uint64_t span = (uint64_t)ECG_LENS_SPAN_COLS * CHUNK_BYTES;
+		const uint64_t *pt = cells + (uint64_t)s * (uint32_t)(k + rows);
+
+		if (b0 >= C)
+			continue;
+		for (uint64_t i = b0 + threadIdx.x; i < (C - b0 < span ? C : b0 + span); i += BLOCK) {
+			uint8_t o[ECG_KMAX_R];
+
+			for (int r = 0; r < ECG_KMAX_R; r++)
+				o[r] = 0;
+			for (int j = 0; j < k; j++) {
+				const uint32_t v = reinterpret_cast<const uint8_t *>(pt[j])[i];
+				for (int r = 0; r < rows; r++)
+					o[r] ^= gf_mul1(P.tbl[r][j], v);
+			}
+			for (int r = 0; r < rows; r++)
+				reinterpret_cast<uint8_t *>(pt[k + r])[i] = o[r];
+		}
+	}
+}
+
+// ---------------------------------------------------------------------------
 // Per-request delta updates (ecg_kabi.h ECG_UPD_REC): the batching queue's
 // device-cell aggregation updates, agg_update_parity's xor_gen +
 // ec_encode_data_update per updated cell (ref:src/object/srv_ec_aggregate.c:
@@ -372,15 +508,24 @@ extern "C" int ecg_k_launch_update_ptrs(const ecg_mm_params_t *p, const uint64_t
 }
 
 typedef void (*mmptr_fn_t)(const ecg_mm_params_t, const uint64_t *);
+typedef void (*mmlens_fn_t)(const ecg_mm_params_t, const uint64_t *, const uint64_t *, const uint64_t *, uint32_t);
 
+// one entry per shape and lane granule: the fixed-length kernel and its
+// per-stripe-length counterpart (lfn, lname)
 struct pentry {
 	int k, r, g;
 	mmptr_fn_t fn;
 	const char *name;
+	mmlens_fn_t lfn;
+	const char *lname;
 };
 
-#define PE(K_, R_) {K_, R_, 16, ecg_mm_ptr_kernel<K_, R_, 16>, "ecg_mm_ptr_kernel<" #K_ "," #R_ ">"}
-#define PEG(K_, R_, G_) {K_, R_, G_, ecg_mm_ptr_kernel<K_, R_, G_>, "ecg_mm_ptr_kernel<" #K_ "," #R_ ",g" #G_ ">"}
+#define PE(K_, R_) \
+	{K_, R_, 16, ecg_mm_ptr_kernel<K_, R_, 16>, "ecg_mm_ptr_kernel<" #K_ "," #R_ ">", \
+	 ecg_mm_ptr_lens_kernel<K_, R_, 16>, "ecg_mm_ptr_lens_kernel<" #K_ "," #R_ ">"}
+#define PEG(K_, R_, G_) \
+	{K_, R_, G_, ecg_mm_ptr_kernel<K_, R_, G_>, "ecg_mm_ptr_kernel<" #K_ "," #R_ ",g" #G_ ">", \
+	 ecg_mm_ptr_lens_kernel<K_, R_, G_>, "ecg_mm_ptr_lens_kernel<" #K_ "," #R_ ",g" #G_ ">"}
 #define PEG_SET(G_) \
 	PEG(2, 1, G_), PEG(2, 2, G_), PEG(2, 3, G_), PEG(4, 1, G_), PEG(4, 2, G_), PEG(4, 3, G_), \
 	PEG(8, 1, G_), PEG(8, 2, G_), PEG(8, 3, G_), PEG(16, 1, G_), PEG(16, 2, G_), PEG(16, 3, G_), PEG(0, 0, G_)
@@ -394,18 +539,32 @@ static const pentry g_pkernels[] = {
 #define N_PKERNELS ((uint32_t)(sizeof(g_pkernels) / sizeof(g_pkernels[0])))
 
 extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t *cells_dev, int granule,
-				       const ecg_launch_cfg_t *cfg, void *stream, const char **kernel)
+				       const uint64_t *lens_dev, const uint64_t *spans_dev, uint32_t nspans,
+				       uint32_t max_cols, const ecg_launch_cfg_t *cfg, void *stream,
+				       const char **kernel)
 {
 	hipStream_t st = (hipStream_t)stream;
+	const bool lens = lens_dev != nullptr;
 	int g = granule;
 	uint32_t id = N_PKERNELS, gx, gy;
 
 	if (p->nstripes == 0 || p->cell_bytes == 0 || p->rows == 0)
 		return (int)hipSuccess;
+	if (lens && nspans == 0)
+		return (int)hipSuccess;
+	if (lens && (spans_dev == nullptr || max_cols == 0 || max_cols > ECG_LENS_SPAN_COLS))
+		return (int)hipErrorInvalidValue;
 	if (g == 16 && (p->cell_bytes & 15u))	// the 16-byte lanes need whole 16-byte pieces
 		g = 4;
 	if (g == 0 || (cfg && cfg->variant == 2)) {	/* 0: the host found operands the
 							 * device cannot serve as dwords */
+		if (lens) {
+			hipLaunchKernelGGL(ecg_mm_ptr_lens_byte_kernel, dim3(nspans < 8192 ? nspans : 8192), dim3(BLOCK),
+					   0, st, *p, cells_dev, lens_dev, spans_dev, nspans);
+			if (kernel)
+				*kernel = "ecg_mm_ptr_lens_byte_kernel";
+			return (int)hipGetLastError();
+		}
 		hipLaunchKernelGGL(ecg_mm_ptr_byte_kernel, dim3(mm_byte_grid(p)), dim3(BLOCK), 0, st, *p, cells_dev);
 		if (kernel)
 			*kernel = "ecg_mm_ptr_byte_kernel";
@@ -428,11 +587,20 @@ extern "C" int ecg_k_launch_matmul_ptrs(const ecg_mm_params_t *p, const uint64_t
 			id = i;
 	if (id == N_PKERNELS)
 		return (int)hipErrorInvalidDeviceFunction;
-	mm_grid(p, cfg, &gx, &gy);
+	if (lens) {	// x over the columns of a span, y over the spans (clamped: the kernel strides)
+		gx = cfg && cfg->grid_x ? cfg->grid_x : max_cols;
+		gy = cfg && cfg->grid_y ? cfg->grid_y : (nspans < 65535 ? nspans : 65535);
+	} else {
+		mm_grid(p, cfg, &gx, &gy);
+	}
 	// blocks per CU as the offset kernel's (ecg_set_wg_per_cu): unused dynamic LDS
 	const size_t lds = mm_dyn_lds(mm_wg_cap(p, cfg, (uint64_t)gx * gy), g_pkernels[id].k, g_pkernels[id].r);
-	hipLaunchKernelGGL(g_pkernels[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev);
+	if (lens)
+		hipLaunchKernelGGL(g_pkernels[id].lfn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev, lens_dev,
+				   spans_dev, nspans);
+	else
+		hipLaunchKernelGGL(g_pkernels[id].fn, dim3(gx, gy), dim3(BLOCK), lds, st, *p, cells_dev);
 	if (kernel)
-		*kernel = g_pkernels[id].name;
+		*kernel = lens ? g_pkernels[id].lname : g_pkernels[id].name;
 	return (int)hipGetLastError();
 }

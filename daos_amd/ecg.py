@@ -84,6 +84,9 @@ _SIGS = [
     ("ecg_erasure_sets", C.c_int, [C.c_int, C.c_int]),
     ("ecg_erasure_set_index", C.c_int, [C.c_int, C.c_int, C.c_uint32]),
     ("ecg_matmul_ptrs", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint64, C.c_uint32, C.POINTER(vp), vp]),
+    ("ecg_matmul_ptrs_lens", C.c_int, [vp, C.c_int, C.c_int, u8p, C.c_uint32, C.POINTER(vp), C.POINTER(C.c_uint64),
+                                       vp]),
+    ("ecg_lens_plan", C.c_int, [C.POINTER(C.c_uint64), C.c_uint32, C.POINTER(C.c_uint64), u32p]),
     ("ecg_update_ptrs", C.c_int, [vp, C.c_int, C.c_int, C.c_uint64, C.c_uint32, C.POINTER(vp), u8p, vp]),
     ("ecg_matmul_host", C.c_int, [vp, C.c_int, C.c_int, C.c_int, u8p, C.POINTER(u8p), C.POINTER(u8p), C.c_uint]),
     ("ecg_cpu_matmul", C.c_int, [C.c_int, C.c_int, C.c_int, u8p, C.POINTER(u8p), C.POINTER(u8p), C.c_uint]),
@@ -179,6 +182,8 @@ _SIGS = [
     ("ecg_agg_recalc_parity", C.c_int, [vp, C.c_uint32, C.c_uint64, u8p, C.c_uint32, u8p, u8p, u8p]),
     ("ecg_obj_ec_singv_cell_bytes", C.c_uint64, [C.c_uint32, C.c_uint64]),
     ("ecg_obj_ec_singv_encode", C.c_int, [C.c_uint32, C.c_uint64, u8p, C.POINTER(u8p)]),
+    ("ecg_obj_ec_singv_encode_dev", C.c_int, [vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(vp),
+                                              C.POINTER(vp), vp]),
     ("ecg_obj_ec_recx_encode", C.c_int, [vp, C.c_uint32, C.c_uint64, vp, C.c_uint32, vp, C.c_uint32,
                                          C.POINTER(vp), vp]),
     ("ecg_obj_ec_stripe_list_init", C.c_int, [C.c_uint64, vp, C.c_uint32, vp, C.c_uint32, u32p]),
@@ -463,6 +468,19 @@ def agg_threshold(k: int, p: int) -> int:
     if n < 0:
         raise EcgError(n, "agg_threshold")
     return n
+
+
+LENS_SPAN_BYTES = 65536     # ECG_LENS_SPAN_BYTES
+
+
+def lens_plan(cell_bytes: Sequence[int]) -> tuple[int, int]:
+    """ecg_lens_plan: (spans, most 4 KiB columns in a span) of Context.matmul_ptrs_lens's launch
+    over these per-stripe cell lengths."""
+    n = len(cell_bytes)
+    arr = (C.c_uint64 * max(1, n))(*cell_bytes)
+    nspans, max_cols = C.c_uint64(), C.c_uint32()
+    _chk(lib().ecg_lens_plan(arr, n, C.byref(nspans), C.byref(max_cols)), "lens_plan")
+    return nspans.value, max_cols.value
 
 
 def erasure_sets(k: int, p: int) -> int:
@@ -917,6 +935,26 @@ class Context:
         co = np.ascontiguousarray(coef, dtype=np.uint8).reshape(-1)
         arr = (vp * len(cells))(*cells)
         _chk(lib().ecg_matmul_ptrs(self.h, k, rows, _u8(co), cell_bytes, nstripes, arr, stream), "matmul_ptrs")
+
+    def matmul_ptrs_lens(self, k: int, rows: int, coef: np.ndarray, cells: Sequence[int | None],
+                         cell_bytes: Sequence[int], stream=None):
+        """ecg_matmul_ptrs_lens: matmul_ptrs() with the cell length of stripe s in cell_bytes[s];
+        a stripe of length 0 is skipped and its entries may be None."""
+        co = np.ascontiguousarray(coef, dtype=np.uint8).reshape(-1)
+        n = len(cell_bytes)
+        arr = (vp * max(1, len(cells)))(*cells)
+        lens = (C.c_uint64 * max(1, n))(*cell_bytes)
+        _chk(lib().ecg_matmul_ptrs_lens(self.h, k, rows, _u8(co), n, arr, lens, stream), "matmul_ptrs_lens")
+
+    def singv_encode_dev(self, oc_id: int, iod_sizes: Sequence[int], values: Sequence[int],
+                         parity: Sequence[int], stream=None):
+        """ecg_obj_ec_singv_encode_dev: single values of one EC class in device memory, values[i]
+        of iod_sizes[i] bytes, parity[i*p + r] its parity cell r of singv cell size."""
+        n = len(iod_sizes)
+        sz = (C.c_uint64 * max(1, n))(*iod_sizes)
+        va = (vp * max(1, n))(*values)
+        pa = (vp * max(1, len(parity)))(*parity)
+        _chk(lib().ecg_obj_ec_singv_encode_dev(self.h, oc_id, n, sz, va, pa, stream), "singv_encode_dev")
 
     def update_ptrs(self, k: int, p: int, cell_bytes: int, reqs: Sequence, stream=None):
         """ecg_update_ptrs: reqs = [(vec_i, old_addr, new_addr, [parity_addr] * p)], device addresses;

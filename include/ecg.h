@@ -813,6 +813,43 @@ int ecg_tune_counters(ecg_ctx_t *ctx, uint64_t *probe_cycles, uint64_t *probe_la
 int ecg_matmul_ptrs(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef,
 		    uint64_t cell_bytes, uint32_t nstripes, void *const *cells, void *stream);
 
+/* ecg_matmul_ptrs with a cell length per stripe: cells is the same table, and
+ * cell_bytes[s] (a host array) the length of every cell of stripe s -- single
+ * values of an EC class, whose cell size follows the value's (ecg_daos.h
+ * ecg_obj_ec_singv_encode_dev), rebuild batches across record sizes, an
+ * object's short last extent.  Stripe s gets the bytes ecg_matmul_ptrs(
+ * cell_bytes[s], nstripes = 1) writes for its row; no byte at or past
+ * cell_bytes[s] of an output cell is written.  A stripe of length 0 is skipped:
+ * its entries are not looked at and may be NULL; all lengths 0 or nstripes = 0
+ * returns 0 and launches nothing.  k <= 16, rows <= 8, any address, any length
+ * (below 2^44).  The table, the lengths and the launch plan are staged
+ * internally in one upload, so the host arrays are free when the call returns.
+ * Asynchronous on `stream`.
+ * A batch whose lengths are all the same and none 0 IS ecg_matmul_ptrs with
+ * that length (same route, same kernel, the affine shortcut included).  Any
+ * other takes one launch of ecg_mm_ptr_lens_kernel: the host cuts every stripe
+ * into spans of ECG_LENS_SPAN_BYTES and a block row takes a span, so small
+ * stripes cost one block each and long ones a block per 4 KiB column.  The
+ * lanes follow the addresses of the stripes that are not skipped as for
+ * ecg_matmul_ptrs, with 16-byte lanes only when every length is a multiple of
+ * 16.  The launch takes no part in the launch tuner (whose shape includes the
+ * cell size); ecg_set_launch's grid_x / grid_y override its grid and variant
+ * 2 forces the byte kernel.  Telemetry: one of `launches`.
+ * -ECG_DER_INVAL ("matmul_ptrs_lens: ..."), checked in this order: k / rows
+ * out of range; coef NULL; cell_bytes NULL with nstripes != 0; a NULL
+ * context; cells NULL; a NULL entry in a stripe of non-zero length (the message
+ * names its index).  Output cells overlapping anything else are the caller's
+ * contract, as for ecg_matmul_ptrs.
+ * ecg_lens_plan is the launch plan, host arithmetic only: a stripe of length L
+ * contributes ceil(L / ECG_LENS_SPAN_BYTES) spans to *nspans, and *max_cols is
+ * the most 4 KiB columns any span holds (1 .. 16; 0 when there is no span).
+ * -ECG_DER_INVAL for a NULL pointer with nstripes != 0. */
+#define ECG_LENS_SPAN_BYTES 65536u   /* 16 columns of 4 KiB: the unit of the launch plan */
+int ecg_matmul_ptrs_lens(ecg_ctx_t *ctx, int k, int rows, const unsigned char *coef,
+			 uint32_t nstripes, void *const *cells, const uint64_t *cell_bytes,
+			 void *stream);
+int ecg_lens_plan(const uint64_t *cell_bytes, uint32_t nstripes, uint64_t *nspans, uint32_t *max_cols);
+
 /* Per-request delta parity updates on DEVICE cells: agg_update_parity's
  * xor_gen(old, new) + ec_encode_data_update(vec_i) of one updated data cell
  * (ref:src/object/srv_ec_aggregate.c:1086-1102), nreq requests in one call:

@@ -178,6 +178,28 @@ uint64_t ecg_obj_ec_singv_cell_bytes(uint32_t oc_id, uint64_t iod_size);
 int ecg_obj_ec_singv_encode(uint32_t oc_id, uint64_t iod_size, const unsigned char *value,
 			    unsigned char *p_bufs[]);
 
+/* ecg_obj_ec_singv_encode for nvalues single values of one EC class held in
+ * DEVICE memory, in one call: values[i] is the device address of value i
+ * (iod_sizes[i] bytes at any alignment), parity[i*p + r] that of its parity
+ * cell r (ecg_obj_ec_singv_cell_bytes(oc_id, iod_sizes[i]) bytes); every value
+ * gets the parity bytes ecg_obj_ec_singv_encode writes for it.  Each value has
+ * its own cell size, so the batch is one ecg_matmul_ptrs_lens launch (ecg.h)
+ * over the values in place: the whole cells of a value are read where they
+ * are, the one cell that straddles its end is gathered into zero-filled
+ * scratch first (one memset, one segment-copy launch), and the cells wholly
+ * past its end point at a shared zero region -- no byte past iod_sizes[i] of a
+ * value buffer reaches the result.  The host arrays are free when the call
+ * returns.  Asynchronous on `stream`.
+ * A value the reference keeps on one target (obj_ec_singv_one_tgt,
+ * ref:src/object/obj_ec.h:409-419) is not EC-encoded at all: filtering those
+ * out is the caller's, as with ecg_obj_ec_singv_encode.
+ * -ECG_DER_INVAL ("singv_encode_dev: ..."): a class that is not EC, a NULL
+ * array with nvalues != 0, a zero iod_size, a NULL value or parity entry (the
+ * message names the value), then a NULL context. */
+int ecg_obj_ec_singv_encode_dev(ecg_ctx_t *ctx, uint32_t oc_id, uint32_t nvalues,
+				const uint64_t *iod_sizes, void *const *values,
+				void *const *parity, void *stream);
+
 /* ---- client full-stripe encode over a scatter-gather list --------------
  * obj_ec_recx_encode + obj_ec_stripe_encode (ref:src/object/cli_ec.c:476-546,
  * 593-663) for an array iod whose sgl and parity buffers are in device
